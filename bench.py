@@ -2,6 +2,7 @@
 """bench.py -- leapfrog steps/sec of VerletSGLDReject on the MI355X path.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload googleresnet|convnet|densenet]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -17,25 +18,36 @@ Default workload: googleresnet on CIFAR-10-shaped batches (BASELINE.json configs
 north-star target workload; it fits one GPU).  ``--workload densenet`` is configs[1],
 ``--workload convnet`` configs[2].
 
-Timed region: after W untimed warm-up steps, BLOCKS of exactly K steps are run back to back
-until at least ``--min-seconds`` (0.5 s) have been timed; the whole region is bracketed by
-barrier + ``torch.cuda.synchronize()`` on both sides and every block boundary carries an event
-on the launch stream.  ``value`` = K / (median block duration), max over ranks; the wall-clock
-rate of the whole region is reported beside it (``wall_steps_per_s``).  With the driver's small
-K the figure therefore does not depend on how long the host needs to fill the launch pipeline.
+Timed region: after W untimed warm-up steps, exactly K steps, bracketed by barrier +
+``torch.cuda.synchronize()`` on both sides with an event on the launch stream at either end.
+``value`` = K / (block duration), max over ranks; ``ms_per_step`` = block duration / K.  With
+``--min-seconds S`` an untimed calibration block is followed by as many blocks of K steps as fill
+S seconds, and ``value`` is K / (median block duration).
+
+``--dump-outputs DIR``: right after the timed steps, what the path computed in its last step --
+parameters, sampler state, gradient, BatchNorm buffers, the metric rows of the timed steps -- is
+written as ``DIR/<name>.npy`` (``step_outputs``).  All inputs are seeded, so two runs with the same
+arguments (of two builds, say) can be compared output for output.
+
+A plain run does only that.  ``--full`` adds everything else the script measures, after the timed
+region: live sampler / convolution / BatchNorm kernel timings and their rooflines, sample cycles
+(with and without M-H, with evaluation and the sample store), the flat-arena point, chains per
+GPU, the other BASELINE workloads as sub-runs, the CPU baseline, and the detail file.
 
 Chains are independent: rank r runs chain r on GPU r with Philox stream r and its own
-synthetic data (seed 1234 + r); no collective on the data path ("scaling": "weak").  After the
-timed region a multi-rank run performs the one exchange the path has -- the posterior-predictive
-ensemble over all chains (two small all-reduces over RCCL) and the sample gather -- on synthetic
-tables, checks it against the single-process formula (reference exp_utils.py:300-321) and reports
-its time separately (``exchange``).  Rank 0 prints ONE JSON line.  See DESIGN.md "Measurement".
+synthetic data (seed 1234 + r); no collective on the data path ("scaling": "weak").  With
+``--full``, after the timed region a multi-rank run performs the one exchange the path has -- the
+posterior-predictive ensemble over all chains (two small all-reduces over RCCL) and the sample
+gather -- on synthetic tables, checks it against the single-process formula (reference
+exp_utils.py:300-321) and reports its time separately (``exchange``).  Rank 0 prints ONE JSON
+line.  See DESIGN.md "Measurement".
 """
 import argparse
 import ctypes
 import json
 import math
 import os
+import re
 import statistics
 import sys
 import time
@@ -67,22 +79,36 @@ WORKLOADS = {
 }
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100, help="K: steps per timed block")
+    ap.add_argument("--steps", type=int, default=100, help="K: timed steps (one block of K steps)")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default="googleresnet", choices=sorted(WORKLOADS))
-    ap.add_argument("--min-seconds", type=float, default=0.5, help="keep timing blocks of K steps until this long")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline (sampler kernel timing and the rooflines, "
+                         "sample cycles, flat-arena point, chains per GPU, other workloads, CPU baseline, the multi-rank "
+                         "solo reference and exchange) and write the detail file; without it a run sets up, warms up, "
+                         "times the K steps and prints its line.  A flag given explicitly holds either way")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed (parameters, sampler state, "
+                         "gradient, buffers, the metric rows of the timed steps) as DIR/<name>.npy")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="after an untimed calibration block, time as many blocks of K steps as fill this long "
+                         "(0 = exactly one block: K timed steps)")
     ap.add_argument("--max-blocks", type=int, default=400)
-    ap.add_argument("--cpu-budget", type=float, default=30.0, help="seconds of CPU baseline, timed as three blocks (0 = skip)")
-    ap.add_argument("--sweep-log2", type=int, default=28, help="flat-arena roofline point, log2(elements); 0 = skip")
-    ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--cpu-budget", type=float, default=None,
+                    help="seconds of CPU baseline, timed as three blocks (0 = skip; default 30 with --full, else 0)")
+    ap.add_argument("--sweep-log2", type=int, default=None,
+                    help="flat-arena roofline point, log2(elements); 0 = skip (default 28 with --full, else 0)")
+    ap.add_argument("--no-kernel-timing", action="store_true",
+                    help="no sampler kernel timing / roofline rows (they run only with --full)")
     ap.add_argument("--eager", action="store_true", help="no hipGraph capture (for comparison)")
     ap.add_argument("--cudnn-benchmark", type=int, default=1,
                     help="MIOpen find mode, as the reference sets it (experiments/train_bnn.py:29-31)")
     ap.add_argument("--channels-last", type=int, default=0)
-    ap.add_argument("--samples", type=int, default=10, help="also time K full sample cycles (0 = skip)")
+    ap.add_argument("--samples", type=int, default=None,
+                    help="also time K full sample cycles (0 = skip; default 10 with --full, else 0)")
     ap.add_argument("--metrics-skip", type=int, default=10, help="BASELINE configs use 10")
     ap.add_argument("--inference", default="VerletSGLDReject",
                     choices=["VerletSGLDReject", "HMCReject", "SGLDReject"],
@@ -97,28 +123,43 @@ def parse():
                     help="googleresnet: every minibatch is gathered from the HBM-resident set through the on-device "
                          "random crop (pad 4) + flip, as configs[3]'s cifar10_augmented (data/CIFAR/cifar.py:136-172)")
     ap.add_argument("--exchange-samples", type=int, default=8, help="synthetic samples per chain in the exchange leg")
-    ap.add_argument("--chain-sweep", default="1,2,4,8",
-                    help="densenet only: aggregate steps/s of K chains sharing ONE GPU's launches (MultiChainDense); '' = skip")
+    ap.add_argument("--chain-sweep", default=None,
+                    help="densenet only: aggregate steps/s of K chains sharing ONE GPU's launches (MultiChainDense); '' = skip "
+                         "(default '1,2,4,8' with --full, else '')")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend of a multi-rank run: nccl = RCCL over xGMI (the product path); gloo = "
                          "the SAME control flow with host collectives, so that two ranks can share one GPU "
                          "(a plumbing check of the multi-rank leg, never a scaling number)")
     ap.add_argument("--other-workloads", type=int, default=None,
                     help="also run BASELINE configs[1], [2], [4] (densenet, convnet, googleresnet HMC L=50 T=0.1) as "
-                         "sub-runs and report them in `other_workloads` (default: on for the default one-GPU run)")
+                         "sub-runs and report them in `other_workloads` (default: on for the default one-GPU run with --full)")
     ap.add_argument("--width", type=int, default=50,
                     help="hidden width of densenet / convnet (experiments/train_bnn.py:53-54 makes it a user option; the "
                          "BASELINE configs use 50).  Widths off the kernel tables run on the library path: needs "
                          "SGMCMC_STRICT=0 in the environment, and the line says so in config.step_path")
     ap.add_argument("--eval-rows", type=int, default=10000,
                     help="rows of the synthetic test set of `samples_per_sec_with_eval` (CIFAR-10's test set: 10,000)")
-    ap.add_argument("--detail", default=os.path.join(ROOT, "bench_detail.json"),
+    ap.add_argument("--detail", default=None,
                     help="side file of the FULL record (per-kernel roofline rows, other workloads, timing, chains per GPU, "
-                         "calibration); stdout carries only the compact line (< 4 KB)")
+                         "calibration); stdout carries only the compact line (< 4 KB).  Default with --full: "
+                         "bench_detail.json beside this script; else none")
     ap.add_argument("--stream-chains", default=None,
                     help="googleresnet / convnet: aggregate steps/s of K chains on K HIP streams of ONE GPU, e.g. '1,2,3' "
-                         "(after the timed region; default: '1,2,4' for a one-GPU googleresnet run, '' = skip)")
-    return ap.parse_args()
+                         "(after the timed region; default with --full: '1,2,4,8' for a one-GPU googleresnet run; '' = skip)")
+    args = ap.parse_args(argv)
+    # the measurements beside the headline: on by default only with --full (an explicit value holds either way)
+    full = args.full
+    for name, on, off in (("cpu_budget", 30.0, 0.0), ("sweep_log2", 28, 0), ("samples", 10, 0),
+                          ("chain_sweep", "1,2,4,8", ""), ("detail", os.path.join(ROOT, "bench_detail.json"), None)):
+        if getattr(args, name) is None:
+            setattr(args, name, on if full else off)
+    if not full:
+        args.no_kernel_timing = True
+        if args.stream_chains is None:
+            args.stream_chains = ""
+        if args.other_workloads is None:
+            args.other_workloads = 0
+    return args
 
 
 class PoolSource:
@@ -681,7 +722,7 @@ def exchange_leg(model, rank, world, device, E, cdev=None, backend="nccl", n_tes
 def other_workloads(args, only=None):
     """BASELINE configs[1], [2] and [4] as sub-runs of this script (fresh processes: their own captured graphs and
     kernel tables), so that the ONE line the driver records carries all four GPU configurations.  Each sub-run times
-    its leapfrog loop exactly as the headline does and K = 10 full sample cycles; no rooflines, no CPU baseline."""
+    blocks of 100 leapfrog steps for at least 0.5 s and K = 10 full sample cycles; no rooflines, no CPU baseline."""
     import subprocess
     subs = {
         "configs[1] densenet VerletSGLDReject": ["--workload", "densenet", "--chain-sweep", ""],
@@ -699,8 +740,8 @@ def other_workloads(args, only=None):
         if only is not None and only not in name:
             continue
         with tempfile.NamedTemporaryFile(suffix=".json", prefix="bench_sub_") as side:
-            cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", "100", "--warmup", "20",
-                   "--cpu-budget", "0", "--sweep-log2", "0", "--no-kernel-timing", "--stream-chains", "", "--samples", "10",
+            cmd = [sys.executable, os.path.abspath(__file__), "--full", "--gpus", "1", "--steps", "100", "--warmup", "20",
+                   "--min-seconds", "0.5", "--cpu-budget", "0", "--sweep-log2", "0", "--no-kernel-timing", "--stream-chains", "", "--samples", "10",
                    "--other-workloads", "0", "--eval-rows", "0", "--metrics-skip", str(args.metrics_skip),
                    "--detail", side.name] + flags
             t0 = time.perf_counter()
@@ -718,6 +759,58 @@ def other_workloads(args, only=None):
             except Exception as exc:      # a sub-run never takes the headline down
                 out[name] = {"error": f"{type(exc).__name__}: {str(exc)[:300]}"}
     return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def step_outputs(runner, model, first_step, last_step):
+    """What a caller of the timed path holds after its last step: the position (every parameter, flattened in
+    ``model.parameters()`` order), the sampler state the optimizer exposes per parameter, the last minibatch
+    gradient, the floating-point buffers (BatchNorm running statistics), and every metric row the timed steps
+    logged (``metric_<name>``, indexed by ``metric_step``).  float32 as computed; the metric rows float64."""
+    import numpy as np
+    params = list(model.parameters())
+
+    def flat(ts):
+        return torch.cat([t.detach().reshape(-1).float() for t in ts]).cpu().numpy() if ts else None
+    out = {"theta": flat(params)}
+    opt = runner.optimizer
+    for key in ("momentum_buffer", "square_avg"):
+        ts = [opt.state[p].get(key) for p in params]
+        if all(isinstance(t, torch.Tensor) for t in ts):
+            out[key] = flat(ts)
+    if all(p.grad is not None for p in params):
+        out["grad"] = flat([p.grad for p in params])
+    bufs = [b for b in model.buffers() if b.is_floating_point()]
+    if bufs:
+        out["buffers"] = flat(bufs)
+    saver = runner.metrics_saver
+    rows = [(s, r) for s, r in saver.rows.items() if first_step <= s <= last_step] if hasattr(saver, "rows") else []
+    if rows:
+        out["metric_step"] = np.array([s for s, _ in rows], dtype=np.float64)
+        for name in sorted({k for _, r in rows for k in r if k != "timestamps"}):
+            # (names such as "acceptance/is_sample" become file names: acceptance.is_sample)
+            out["metric_" + re.sub(r"[^0-9A-Za-z_.-]", ".", name)] = np.array([float(r.get(name, np.nan)) for _, r in rows],
+                                                                               dtype=np.float64)
+    return {k: v for k, v in out.items() if v is not None}
+
+
+def dump_outputs(directory, arrays, limit=DUMP_LIMIT_BYTES):
+    """``directory/<name>.npy`` for every array; above ``limit`` bytes in all, every array is cut to the same fixed,
+    seeded sample fraction of its elements (their positions as ``<name>_index.npy``)"""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    keep = 1.0 if total <= limit else limit / sum(a.nbytes + 8 * a.size for a in arrays.values())  # (+ float64 index)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a).reshape(-1)
+        if keep < 1.0:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, max(1, int(a.size * keep)), replace=False))
+            a = a[idx]
+            np.save(os.path.join(directory, name + "_index.npy"), idx.astype(np.float64))
+        np.save(os.path.join(directory, name + ".npy"), a)
+    return sorted(arrays)
 
 
 def _library_calls():
@@ -1031,23 +1124,25 @@ def main():
     runner._drain_rows()
     stream = torch.cuda.current_stream(device)
     K = args.steps
-    # how many blocks of K steps make up >= min-seconds: one untimed calibration block, rank 0's clock decides
-    torch.cuda.synchronize(device)
-    t0 = time.perf_counter()
-    step = run(K, step)
-    runner._drain_rows()
-    torch.cuda.synchronize(device)
-    n_blocks = max(1, min(args.max_blocks, math.ceil(args.min_seconds / max(time.perf_counter() - t0, 1e-6))))
+    n_blocks = 1                  # the default: exactly K timed steps
+    if args.min_seconds > 0:
+        # how many blocks of K steps make up >= min-seconds: one untimed calibration block, rank 0's clock decides
+        torch.cuda.synchronize(device)
+        t0 = time.perf_counter()
+        step = run(K, step)
+        runner._drain_rows()
+        torch.cuda.synchronize(device)
+        n_blocks = max(1, min(args.max_blocks, math.ceil(args.min_seconds / max(time.perf_counter() - t0, 1e-6))))
     if distributed:
         nb = torch.tensor([n_blocks], device=cdev)
         dist.broadcast(nb, src=0)
         n_blocks = int(nb.item())
         dist.barrier()
-    # Multi-rank runs: rank 0 first times the same blocks ALONE (the other ranks wait at a barrier, their GPUs idle) -- the
-    # per-GPU rate that the N-rank region's per-rank rates are set against (efficiency_vs_solo in the line; the driver
-    # computes its own scaling efficiency from the per-N values of separate runs)
+    # Multi-rank runs with --full: rank 0 first times the same blocks ALONE (the other ranks wait at a barrier, their GPUs
+    # idle) -- the per-GPU rate that the N-rank region's per-rank rates are set against (efficiency_vs_solo in the line;
+    # the driver computes its own scaling efficiency from the per-N values of separate runs)
     solo_ms = None
-    if distributed and world > 1:
+    if distributed and world > 1 and args.full:
         if rank == 0:
             torch.cuda.synchronize(device)
             sm = [torch.cuda.Event(enable_timing=True)]
@@ -1065,6 +1160,7 @@ def main():
     marks = [torch.cuda.Event(enable_timing=True)]
     marks[0].record(stream)
     t0 = time.perf_counter()
+    first_timed = step + 1
     for _ in range(n_blocks):
         step = run(K, step)
         ev = torch.cuda.Event(enable_timing=True)
@@ -1089,6 +1185,8 @@ def main():
     dt_block = med_ms * 1e-3
 
     runner._check_finite()
+    if args.dump_outputs and rank == 0:        # before anything below takes further steps on this chain
+        dump_outputs(args.dump_outputs, step_outputs(runner, model, first_timed, step))
     # Live duration of the fused sampler kernel: a node inside a graph replay cannot carry events, so the same
     # launches (same arena, same arguments) are issued right here, each with a start / stop event in its
     # dispatch packet.  rocprofv3's per-dispatch durations of the in-graph launches are in profiles/.
@@ -1161,7 +1259,8 @@ def main():
             runner.dataloader_test, runner.model_saver = empty_test, None
             import shutil
             shutil.rmtree(tmp, ignore_errors=True)
-    exchange = exchange_leg(model, rank, world, device, args.exchange_samples, cdev, args.backend) if distributed else None
+    exchange = (exchange_leg(model, rank, world, device, args.exchange_samples, cdev, args.backend)
+                if distributed and args.full else None)
 
     ranks_seen, devices = 1, [{"rank": 0, "local_rank": local, "device": torch.cuda.get_device_name(device),
                                "index": device.index}]
@@ -1193,9 +1292,9 @@ def main():
                    "median_block_ms": round(med_ms, 4), "min_block_ms": round(min(block_ms), 4),
                    "max_block_ms": round(max(block_ms), 4), "region_wall_s": round(wall, 4),
                    "wall_steps_per_s": round(world * n_blocks * K / wall, 2),
-                   "method": "blocks of K steps back to back, event on the launch stream at every block "
-                             "boundary, region bracketed by barrier + synchronize; value = K / median block "
-                             "(max over ranks)"},
+                   "method": "one block of K steps (--min-seconds > 0: blocks of K steps back to back), event on the "
+                             "launch stream at every block boundary, region bracketed by barrier + synchronize; "
+                             "value = K / median block (max over ranks)"},
     }
     if pinned_cpus is not None:
         out["config"]["cpus_per_rank"] = pinned_cpus

@@ -174,7 +174,7 @@ def test_gpus_2_over_gloo_starts_two_ranks_by_itself(tmp_path):
     """`python bench.py --gpus 2` with no launcher around it: two ranks, one chain each, the exchange checked against the
     single-process formula (over gloo the two ranks share this box's one GPU: plumbing, never a scaling number)."""
     detail = tmp_path / "detail.json"
-    line = _run_bench("--gpus", "2", "--backend", "gloo", "--steps", "5", "--warmup", "2", "--samples", "0",
+    line = _run_bench("--full", "--gpus", "2", "--backend", "gloo", "--steps", "5", "--warmup", "2", "--samples", "0",
                       "--cpu-budget", "0", "--other-workloads", "0", "--sweep-log2", "0", "--no-kernel-timing",
                       "--stream-chains", "", "--detail", str(detail))
     assert line["n_gpus"] == 2 and line["ranks_seen"] == 2 and line["backend"] == "gloo"
@@ -191,7 +191,7 @@ def test_gpus_2_over_gloo_starts_two_ranks_by_itself(tmp_path):
 @pytest.mark.gpu
 def test_one_gpu_line_carries_roofline_and_names_its_detail_file(tmp_path):
     detail = tmp_path / "detail.json"
-    line = _run_bench("--steps", "5", "--warmup", "2", "--samples", "0", "--cpu-budget", "0", "--other-workloads", "0",
+    line = _run_bench("--full", "--steps", "5", "--warmup", "2", "--samples", "0", "--cpu-budget", "0", "--other-workloads", "0",
                       "--sweep-log2", "20", "--stream-chains", "", "--detail", str(detail))
     assert line["n_gpus"] == 1 and line["ranks_seen"] == 1
     assert line["roofline"]["bound"] in ("hbm", "mfma") and 0 < line["roofline"]["frac"] <= 1
@@ -209,3 +209,92 @@ def test_a_sub_run_of_other_workloads_is_read_from_its_side_file():
     (name, row), = got.items()
     assert "error" not in row, row
     assert row["value"] > 0 and row["timed_steps"] > 0 and "dense" in row["step_path"]
+
+
+def test_a_plain_run_is_the_headline_alone_and_full_restores_every_leg():
+    """`bench.py --steps K --warmup W` times exactly K steps and nothing else; `--full` turns every other measurement
+    back on with its earlier default; a value given explicitly holds either way"""
+    plain = bench.parse(["--steps", "7", "--warmup", "3"])
+    assert plain.steps == 7 and plain.warmup == 3 and plain.min_seconds == 0 and not plain.full
+    assert plain.no_kernel_timing and plain.samples == 0 and plain.cpu_budget == 0 and plain.sweep_log2 == 0
+    assert plain.chain_sweep == "" and plain.stream_chains == "" and plain.other_workloads == 0
+    assert plain.detail is None and plain.dump_outputs is None
+    full = bench.parse(["--full"])
+    assert not full.no_kernel_timing and full.samples == 10 and full.cpu_budget == 30.0 and full.sweep_log2 == 28
+    assert full.chain_sweep == "1,2,4,8" and full.stream_chains is None and full.other_workloads is None
+    assert full.detail == os.path.join(ROOT, "bench_detail.json")
+    assert bench.parse(["--samples", "3"]).samples == 3 and bench.parse(["--full", "--cpu-budget", "0"]).cpu_budget == 0
+    assert bench.parse(["--dump-outputs", "out"]).dump_outputs == "out"
+
+
+def test_dump_outputs_keeps_a_fixed_sample_within_its_limit(tmp_path):
+    import numpy as np
+    arrays = {"theta": np.arange(1000, dtype=np.float32), "metric_loss": np.linspace(0, 1, 300)}
+    assert bench.dump_outputs(str(tmp_path / "whole"), arrays) == ["metric_loss", "theta"]
+    for name, a in arrays.items():
+        got = np.load(tmp_path / "whole" / f"{name}.npy")
+        assert got.dtype == a.dtype and np.array_equal(got, a)
+    assert not list((tmp_path / "whole").glob("*_index.npy"))
+    limit = 4000
+    for d in ("cut1", "cut2"):
+        bench.dump_outputs(str(tmp_path / d), arrays, limit=limit)
+    total = 0
+    for name, a in arrays.items():
+        got, idx = np.load(tmp_path / "cut1" / f"{name}.npy"), np.load(tmp_path / "cut1" / f"{name}_index.npy")
+        assert got.dtype == a.dtype and idx.dtype == np.float64 and 0 < len(got) < len(a)
+        assert np.array_equal(got, a[idx.astype(np.int64)])
+        assert np.array_equal(got, np.load(tmp_path / "cut2" / f"{name}.npy"))        # the same sample every time
+        total += got.nbytes + idx.nbytes
+    assert total <= limit
+
+
+@pytest.mark.gpu
+def test_a_plain_run_times_its_steps_and_dumps_the_same_outputs_twice(tmp_path):
+    import numpy as np
+    lines = [_run_bench("--gpus", "1", "--steps", "12", "--warmup", "3", "--dump-outputs", str(tmp_path / d))
+             for d in ("one", "two")]
+    line = lines[0]
+    assert line["steps"] == 12 and line["warmup"] == 3 and line["unit"] == "steps/s" and line["dtype"] == "f32"
+    assert line["higher_is_better"] is True and line["metric"].startswith("leapfrog steps/sec")
+    assert line["ms_per_step"] == pytest.approx(1e3 / line["value"], rel=1e-3)
+    for k in ("roofline", "roofline_sampler", "roofline_flat_arena", "cpu_baseline", "samples_per_sec", "chains_per_gpu",
+              "other_workloads", "exchange"):
+        assert k not in line, k
+    assert line["detail"] is None
+    names = sorted(os.listdir(tmp_path / "one"))
+    assert names == sorted(os.listdir(tmp_path / "two"))
+    assert {"theta.npy", "momentum_buffer.npy", "grad.npy", "buffers.npy", "metric_step.npy", "metric_loss.npy"} <= set(names), names
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "one" / n), np.load(tmp_path / "two" / n)
+        assert a.dtype in (np.float32, np.float64), (n, a.dtype)
+        np.testing.assert_array_equal(a, b, err_msg=n)        # same arguments, same inputs: the same bits
+        total += a.nbytes
+    assert total <= 64 << 20
+    theta = np.load(tmp_path / "one" / "theta.npy")
+    assert theta.size == line["config"]["params"] and np.isfinite(theta).all()
+
+
+def test_step_outputs_are_what_the_caller_holds_named_as_files():
+    import types
+    import numpy as np
+    import torch
+    from bnn_priors_amd.storage import MemoryMetrics
+    model = torch.nn.Sequential(torch.nn.Linear(3, 2), torch.nn.BatchNorm1d(2))
+    params = list(model.parameters())
+    for p in params:
+        p.grad = torch.full_like(p, 0.5)
+    opt = types.SimpleNamespace(state={p: {"momentum_buffer": torch.ones_like(p)} for p in params})
+    saver = MemoryMetrics()
+    for step in (10, 20, 30):
+        saver.add_scalar("loss", step / 10, step)
+        saver.add_scalar("acceptance/is_sample", 0, step)
+    got = bench.step_outputs(types.SimpleNamespace(optimizer=opt, metrics_saver=saver), model, 15, 30)
+    assert set(got) == {"theta", "momentum_buffer", "grad", "buffers", "metric_step", "metric_loss",
+                        "metric_acceptance.is_sample"}
+    n = sum(p.numel() for p in params)
+    assert got["theta"].dtype == np.float32 and got["theta"].shape == (n,)
+    assert np.array_equal(got["theta"], torch.cat([p.detach().reshape(-1) for p in params]).numpy())
+    assert np.all(got["momentum_buffer"] == 1) and np.all(got["grad"] == 0.5) and got["buffers"].size == 4   # (running mean, var)
+    assert got["metric_step"].tolist() == [20.0, 30.0] and got["metric_loss"].tolist() == [2.0, 3.0]
+    assert got["metric_loss"].dtype == np.float64

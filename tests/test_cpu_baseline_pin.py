@@ -4,8 +4,9 @@ reference's own loop body (bnn_priors/inference_reject.py:86-113, inference.py:2
 * ``test_cpu_leapfrog_matches_reference_fixture`` (runs everywhere): K steps of ``cpu_leapfrog`` on the oracle's own
   plain-torch network (oracle/nets.py; a reference-shaped model only supplies the initial values) reproduce the parameter vector / potentials / delta_energy that the IMPORTED REFERENCE
   produced for the same inputs and torch seed (tests/golden/cpu_loop.npz, make_cpu_loop_golden.py);
-* ``test_cpu_leapfrog_matches_imported_reference`` (needs /root/reference): the same comparison live,
-  statement for statement, bit for bit.
+* ``test_cpu_leapfrog_matches_imported_reference``: the same comparison bit for bit -- the fixture holds exactly what
+  the imported reference's loop body (``reference_loop``, single-threaded) returned, so with the same op sequence on the
+  same BLAS build nothing may differ.
 """
 import os
 
@@ -123,23 +124,19 @@ def test_cpu_leapfrog_matches_reference_fixture(golden_dir):
     assert len(des) == K_STEPS // LOOP_KW["metrics_skip"]
 
 
-@pytest.mark.reference
-def test_cpu_leapfrog_matches_imported_reference():
-    import sys
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
-    import ref_stubs
-    ref_stubs.install()
-    import bnn_priors.exp_utils as ref_exp
+def test_cpu_leapfrog_matches_imported_reference(golden_dir):
     from bnn_priors_amd import models
     old = torch.get_num_threads()
     torch.set_num_threads(1)
     try:
-        batches, make_ref = loop_inputs(ref_exp)
-        _, make_own = loop_inputs(models)
-        t_ref, p_ref, d_ref = reference_loop(make_ref(), batches, K_STEPS, **LOOP_KW)
+        batches, make_own = loop_inputs(models)
         t_own, p_own, d_own = oracle_loop(make_own(), batches, K_STEPS, **LOOP_KW)
     finally:
         torch.set_num_threads(old)
+    # the reference's own loop, recorded single-threaded by tests/golden/make_cpu_loop_golden.py (float64 holds
+    # every float32 parameter and every Python float exactly)
+    z = np.load(os.path.join(golden_dir, "cpu_loop.npz"))
+    t_ref, p_ref, d_ref = z["theta"], z["potentials"].tolist(), z["delta_energy"]
     assert np.array_equal(t_ref, t_own)                     # bit for bit: identical op sequence
     assert p_ref == p_own
     np.testing.assert_allclose(d_own, d_ref, rtol=1e-12)

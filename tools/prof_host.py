@@ -1,5 +1,5 @@
 import cProfile, pstats, sys, io
-sys.argv = ["bench.py", "--steps", "4000", "--warmup", "300", "--cpu-budget", "0", "--sweep-log2", "0", "--no-kernel-timing"]
+sys.argv = ["bench.py", "--full", "--steps", "4000", "--warmup", "300", "--cpu-budget", "0", "--sweep-log2", "0", "--no-kernel-timing"]
 sys.path.insert(0, "/root/repo")
 import bench
 pr = cProfile.Profile()

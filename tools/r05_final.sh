@@ -22,11 +22,11 @@ done
 python tools/pmc_to_json.py $P/conv_kernels_pmc_hbm.txt $P/bn_16x32_pmc_hbm.txt $P/bn_32x16_pmc_hbm.txt $P/bn_64x8_pmc_hbm.txt > $P/pmc_traffic.json
 cp $P/pmc_traffic.json profiles/pmc_traffic.json
 find $P -name '*.csv' -size +2M -delete
-python bench.py --gpus 1 --steps 20 --warmup 5 --detail $OUT/bench_googleresnet_driver_args_detail.json > $OUT/bench_googleresnet_driver_args.json 2> $OUT/bench_googleresnet.err
-python bench.py --workload densenet --other-workloads 0 --eval-rows 0 --detail $OUT/bench_densenet_detail.json > $OUT/bench_densenet.json 2> $OUT/bench_densenet.err
-python bench.py --workload convnet --stream-chains 1,2,4 --other-workloads 0 --detail $OUT/bench_convnet_detail.json > $OUT/bench_convnet.json 2> $OUT/bench_convnet.err
-python bench.py --inference HMCReject --trajectory 50 --temperature 0.1 --other-workloads 0 --cpu-budget 0 --sweep-log2 0 --no-kernel-timing --detail $OUT/bench_hmc_detail.json > $OUT/bench_googleresnet_hmc_L50_T0.1.json 2> $OUT/bench_hmc.err
-timeout 600 python bench.py --gpus 2 --backend gloo --steps 20 --warmup 5 --cpu-budget 0 --sweep-log2 0 --samples 0 --other-workloads 0 --no-kernel-timing --detail $OUT/bench_2rank_detail.json > $OUT/bench_2rank_gloo_plumbing.json 2> $OUT/bench_2rank.err
+python bench.py --full --gpus 1 --steps 20 --warmup 5 --detail $OUT/bench_googleresnet_driver_args_detail.json > $OUT/bench_googleresnet_driver_args.json 2> $OUT/bench_googleresnet.err
+python bench.py --full --workload densenet --other-workloads 0 --eval-rows 0 --detail $OUT/bench_densenet_detail.json > $OUT/bench_densenet.json 2> $OUT/bench_densenet.err
+python bench.py --full --workload convnet --stream-chains 1,2,4 --other-workloads 0 --detail $OUT/bench_convnet_detail.json > $OUT/bench_convnet.json 2> $OUT/bench_convnet.err
+python bench.py --full --inference HMCReject --trajectory 50 --temperature 0.1 --other-workloads 0 --cpu-budget 0 --sweep-log2 0 --no-kernel-timing --detail $OUT/bench_hmc_detail.json > $OUT/bench_googleresnet_hmc_L50_T0.1.json 2> $OUT/bench_hmc.err
+timeout 600 python bench.py --full --gpus 2 --backend gloo --steps 20 --warmup 5 --cpu-budget 0 --sweep-log2 0 --samples 0 --other-workloads 0 --no-kernel-timing --detail $OUT/bench_2rank_detail.json > $OUT/bench_2rank_gloo_plumbing.json 2> $OUT/bench_2rank.err
 for L in 1 2 3; do for G in 1 auto; do
   SGMCMC_EXACT_LANES=$L SGMCMC_EXACT_GROUP=$G python tools/exact_pass_probe.py --passes 4 2>/dev/null | tail -1
 done; done > $OUT/exact_pass_lanes_groups_sweep.txt

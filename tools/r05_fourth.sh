@@ -5,7 +5,7 @@ OUT=gpurun_out/r05_fourth
 mkdir -p $OUT
 python -m pytest tests -q -m gpu --durations=8 2>&1 | tail -25 > $OUT/gputests.log
 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
-python bench.py --gpus 1 --steps 20 --warmup 5 --detail $OUT/bench_detail.json > $OUT/bench_line.json 2> $OUT/bench.err
+python bench.py --full --gpus 1 --steps 20 --warmup 5 --detail $OUT/bench_detail.json > $OUT/bench_line.json 2> $OUT/bench.err
 wc -c $OUT/bench_line.json
 KEEP_TRACE=1 bash tools/prof_workload.sh googleresnet $OUT/prof_googleresnet 60 20 --other-workloads 0 > /dev/null 2>&1
 python tools/step_summary.py $OUT/prof_googleresnet/kt_kernel_trace.csv --steps 40 --json $OUT/in_step_us.json --source profiles/r05_googleresnet_steady_state_summary.txt > /dev/null
