@@ -24,7 +24,7 @@ INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 SOURCES = [os.path.join(_HERE, "csrc", "sgmcmc_hip.hip")]
 SOURCE = SOURCES[0]
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 CHUNK = 4096
 CHUNK_SMALL = 1024
 NSUMS = 6
@@ -38,7 +38,10 @@ DEFER_FINALIZE = 256
 INLINE_PRIOR = 512
 PRIOR_NONE, PRIOR_NORMAL, PRIOR_LAPLACE, PRIOR_STUDENT_T, PRIOR_CAUCHY, PRIOR_GENNORM = 0, 1, 2, 3, 4, 5
 PRIOR_GAMMA_SOFTPLUS, PRIOR_UNIFORM_CDF, PRIOR_HALFCAUCHY_SOFTPLUS, PRIOR_IMPROPER_SOFTPLUS = 6, 7, 8, 9
+PRIOR_FILTER_WHITENED = 10
 PRIOR_HAS_LINKS, PRIOR_FULL = 1, 2
+FILTER_MAX_P = 25
+FILTER_BASE_NORMAL, FILTER_BASE_GENNORM = 0, 1
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
                "-fhip-fp32-correctly-rounded-divide-sqrt", "-fPIC", "-shared"]
@@ -52,7 +55,10 @@ CHUNK_DTYPE = np.dtype([("seg", "<i4"), ("n_valid", "<i4")], align=True)
 SEG_STATE_FIELDS = ("sum_gg", "sum_gmo", "sum_gmn", "sum_momo", "sum_mnmn", "sum_thg",
                     "delta_energy", "prev_delta", "est_temperature", "est_config_temp",
                     "point_energy", "aux")
-assert SEGMENT_DTYPE.itemsize == 80 and CHUNK_DTYPE.itemsize == 8
+# sgmcmc_filter_prior: one record per segment, read for SGMCMC_PRIOR_FILTER_WHITENED segments only
+FILTER_DTYPE = np.dtype([("P", "<i4"), ("base", "<i4"), ("beta", "<f8"), ("base_scale", "<f8"), ("lognorm", "<f8"),
+                         ("mu", "<f8", (FILTER_MAX_P,)), ("W", "<f8", (FILTER_MAX_P * FILTER_MAX_P,))], align=True)
+assert SEGMENT_DTYPE.itemsize == 80 and CHUNK_DTYPE.itemsize == 8 and FILTER_DTYPE.itemsize == 5232
 
 
 class Layout(ctypes.Structure):
@@ -61,7 +67,8 @@ class Layout(ctypes.Structure):
                 ("m", ctypes.c_void_p), ("v", ctypes.c_void_p), ("prev_theta", ctypes.c_void_p),
                 ("prev_g", ctypes.c_void_p), ("prev_m", ctypes.c_void_p),
                 ("partials", ctypes.c_void_p), ("state", ctypes.c_void_p),
-                ("scalars", ctypes.c_void_p), ("prior_flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+                ("scalars", ctypes.c_void_p), ("prior_flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("filters", ctypes.c_void_p)]
 
 
 class StepArgs(ctypes.Structure):

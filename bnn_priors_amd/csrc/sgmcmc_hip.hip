@@ -1076,8 +1076,66 @@ __device__ __forceinline__ double prior_log_norm(const sgmcmc_segment& s, double
   return 0.0;
 }
 
+// SGMCMC_PRIOR_FILTER_WHITENED (include/sgmcmc_hip.h): this chunk's elements of segment s.  Element j of the segment
+// belongs to filter f = j / P at position q = j mod P; it re-reads its filter's P values from theta (a filter straddles
+// chunk boundaries: P does not divide the chunk), whitens them, z = (theta_f - mu) W, and adds
+// -(1/N) sum_k psi(z_k) W[q][k] to g[j] -- everything in fp64, one rounding into g.  The log-density partial is
+// base(z_q) + lognorm / P, so the P elements of a filter together carry its whole log-density.  W and mu are staged in
+// LDS (uniform reads); the P values of the filter live in registers (P <= SGMCMC_FILTER_MAX_P).
+template <typename T>
+__device__ __forceinline__ void filter_prior_chunk(const sgmcmc_layout& L, const ChunkCtx& cx,
+                                                   const sgmcmc_segment* __restrict__ sp, double num_data,
+                                                   bool calc_logp, double& lp) {
+  constexpr int kMaxP = SGMCMC_FILTER_MAX_P;
+  __shared__ double sW[kMaxP * kMaxP], smu[kMaxP];
+  const sgmcmc_filter_prior* __restrict__ fp = L.filters + cx.seg;
+  const int P = fp->P;
+  for (int i = threadIdx.x; i < P * P; i += kThreads) sW[i] = fp->W[i];
+  if (threadIdx.x < P) smu[threadIdx.x] = fp->mu[threadIdx.x];
+  __syncthreads();
+  const bool gn = fp->base == SGMCMC_FILTER_BASE_GENNORM;
+  const double beta = fp->beta, inv_bs = 1.0 / fp->base_scale, ln_pos = fp->lognorm / (double)P;
+  const double inv_n = 1.0 / num_data;
+  const T* __restrict__ th = (const T*)sp->theta;
+  T* __restrict__ gp = (T*)sp->g;
+  for (int it = 0; it < items_of(L); ++it) {
+    const int j0 = (it * kThreads + threadIdx.x) * 4;
+    if (j0 >= cx.n_valid) break;
+#pragma unroll 1
+    for (int l = 0; l < 4; ++l) {
+      if (j0 + l >= cx.n_valid) break;
+      const int64_t e = cx.seg_off + j0 + l;      // element of the segment; its filter is [f0, f0 + P) (numel % P == 0)
+      const int q = (int)(e % P);
+      const int64_t f0 = e - q;
+      double d[kMaxP];
+#pragma unroll
+      for (int i = 0; i < kMaxP; ++i)
+        if (i < P) d[i] = (double)th[f0 + i] - smu[i];
+      double gs = 0.0;
+      for (int k = 0; k < P; ++k) {
+        double z = 0.0;
+#pragma unroll
+        for (int i = 0; i < kMaxP; ++i)
+          if (i < P) z = fma(d[i], sW[i * P + k], z);
+        double psi, b = 0.0;
+        if (gn) {
+          const double a = fabs(z) * inv_bs;
+          psi = z == 0.0 ? 0.0 : -copysign(beta * inv_bs * pow_noinline(a, beta - 1.0), z);
+          if (calc_logp && k == q) b = -pow_noinline(a, beta);
+        } else {
+          psi = -z;
+          b = -0.5 * z * z;
+        }
+        gs = fma(psi, sW[q * P + k], gs);
+        if (calc_logp && k == q) lp += b + ln_pos;
+      }
+      gp[e] = (T)((double)gp[e] - gs * inv_n);
+    }
+  }
+}
+
 // FULL = false: only the constant-scale families Normal / Laplace / Student-t / Cauchy (BASELINE's configs): the
-// lean variant the host selects unless some segment has a generalised-normal, hierarchical or hyper prior
+// lean variant the host selects unless some segment has a generalised-normal, hierarchical, hyper or filter prior
 template <typename T, bool FULL>
 __device__ __forceinline__ void prior_body(const sgmcmc_layout& L, double num_data, bool calc_logp,
                                            const GradParts& G) {
@@ -1087,7 +1145,10 @@ __device__ __forceinline__ void prior_body(const sgmcmc_layout& L, double num_da
   const bool parts = G.gpart != nullptr;
   const bool linked = FULL && sp->scale_link > 0;
   double acc[2] = {0.0, 0.0};   // log-density partial; d/dscale of it (hierarchical scales)
-  if ((sp->prior_kind != SGMCMC_PRIOR_NONE || parts) && sp->g != nullptr) {
+  if (FULL && sp->prior_kind == SGMCMC_PRIOR_FILTER_WHITENED) {
+    // (a segment-level branch: the record is read only here; sgmcmc_prior_grad launches this kernel for such tables)
+    if (sp->g != nullptr) filter_prior_chunk<T>(L, cx, sp, num_data, calc_logp, acc[0]);
+  } else if ((sp->prior_kind != SGMCMC_PRIOR_NONE || parts) && sp->g != nullptr) {
     T* __restrict__ gp = (T*)sp->g + cx.seg_off;
     const T* __restrict__ thp = (const T*)sp->theta + cx.seg_off;
     const float* __restrict__ pp = parts ? G.gpart + sp->noise_base + cx.seg_off : nullptr;
@@ -1442,6 +1503,8 @@ int sgmcmc_prior_grad(const sgmcmc_layout* L, double num_data, int calc_log_prob
   const GradParts none = {nullptr, 0, 0, nullptr, nullptr, 1, 1.0};
   flags |= L->prior_flags;
   const bool full = (flags & (SGMCMC_PRIOR_HAS_LINKS | SGMCMC_PRIOR_FULL)) != 0;
+  // a filter table is only ever read by the full kernel (FILTER_WHITENED > CAUCHY sets SGMCMC_PRIOR_FULL)
+  if (L->filters != nullptr && !(L->prior_flags & SGMCMC_PRIOR_FULL)) return (int)hipErrorInvalidValue;
   if (L->dtype == SGMCMC_F32) {
     if (full) SGMCMC_LAUNCH((prior_kernel<float, true>), grid, block, 0, s, *L, num_data, calc_log_prob, none);
     else SGMCMC_LAUNCH((prior_kernel<float, false>), grid, block, 0, s, *L, num_data, calc_log_prob, none);

@@ -185,6 +185,7 @@ class Engine:
             setattr(L, name, t.data_ptr() if t is not None else self.m.data_ptr())
         L.partials, L.state, L.scalars = (self.partials.data_ptr(), self.state_dev.data_ptr(),
                                           self.scalars.data_ptr())
+        L.filters = self._filter_dev.data_ptr() if self._filter_dev is not None else None
 
     # ------------------------------------------------------------------ table refresh
     def stream(self):
@@ -248,9 +249,11 @@ class Engine:
         ev = getattr(self, "_upload_event", None)
         return ev is not None and not ev.query()
 
-    def set_priors(self, specs, links=None):
+    def set_priors(self, specs, links=None, filters=None):
         """specs[i] = None or (kind, loc, scale, shape-parameter): enable the in-kernel prior gradient;
-        links[i] = index of the hyper segment whose VALUE is segment i's scale (hierarchical priors), or None"""
+        links[i] = index of the hyper segment whose VALUE is segment i's scale (hierarchical priors), or None;
+        filters[i] = the whitening of a PRIOR_FILTER_WHITENED segment (``Prior.fused_filter_spec()``), or None"""
+        self._set_filters(specs, filters)
         self.prior_links = False
         for i, sp in enumerate(specs):
             row = self.seg_host[i]
@@ -266,7 +269,49 @@ class Engine:
         # the layout says which prior code its table needs: lean-only entry points refuse the rest (no silent
         # Student-t evaluation of a generalised normal, no NaN placeholder scale of a linked segment)
         self.layout.prior_flags = self.prior_flags()
+        # a filter segment's elements read their neighbours' theta: only the full prior kernel (a launch that does not
+        # write theta) evaluates it, never the in-flight prior of the update kernels -- which PRIOR_FULL refuses
+        assert self._filter_dev is None or self.layout.prior_flags & _hip.PRIOR_FULL
         self._seg_dirty = True
+
+    _filter_dev = None       # device copy of filter_host (one buffer, rewritten in place)
+
+    def _set_filters(self, specs, filters):
+        if filters is None or all(f is None for f in filters):
+            self.filter_host, self._filter_dev = None, None
+            self.layout.filters = None
+            return
+        host = np.zeros(self.n_seg, dtype=_hip.FILTER_DTYPE)
+        for i, f in enumerate(filters):
+            if f is not None:
+                assert specs[i] is not None and int(specs[i][0]) == _hip.PRIOR_FILTER_WHITENED
+                self._filter_row(host[i], i, f)
+        self.filter_host = host
+        if self._filter_dev is None or self._filter_dev.numel() != host.nbytes:
+            self._filter_dev = torch.empty(host.nbytes, dtype=torch.uint8, device=self.device)
+        self._filter_dev.copy_(torch.from_numpy(host.view(np.uint8).copy()))
+        self.layout.filters = self._filter_dev.data_ptr()
+
+    def _filter_row(self, row, i, f):
+        P = int(f["P"])
+        W, mu = np.asarray(f["W"], dtype=np.float64), np.asarray(f["mu"], dtype=np.float64)
+        if not 1 <= P <= _hip.FILTER_MAX_P or W.shape != (P, P) or mu.shape != (P,) or self.params[i].numel() % P:
+            raise ValueError(f"segment {i}: a filter prior needs 1 <= P <= {_hip.FILTER_MAX_P} positions, a P x P "
+                             f"whitening and P locations, and a multiple of P elements (P = {P})")
+        row["P"], row["base"] = P, int(f["base"])
+        row["beta"], row["base_scale"], row["lognorm"] = float(f["beta"]), float(f["base_scale"]), float(f["lognorm"])
+        row["mu"][:] = 0.0
+        row["W"][:] = 0.0
+        row["mu"][:P] = mu
+        row["W"][:P * P] = W.reshape(-1)
+
+    def update_filter(self, i, f):
+        """rewrite segment i's whitening in place (``ConvCovariance.assign_cov``): the device buffer keeps its
+        address, so captured graphs read the new record at their next replay"""
+        row = self.filter_host[i]
+        self._filter_row(row, i, f)
+        n = _hip.FILTER_DTYPE.itemsize
+        self._filter_dev[i * n:(i + 1) * n].copy_(torch.from_numpy(self.filter_host[i:i + 1].view(np.uint8).copy()))
 
     def prior_flags(self):
         return ((_hip.PRIOR_HAS_LINKS if self.prior_links else 0)

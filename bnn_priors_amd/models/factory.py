@@ -2,7 +2,7 @@
 
 Restates the on-path part of ``bnn_priors/exp_utils.py:63-69,99-105,108-234``:
 ``get_model`` for classificationdensenet / classificationconvnet / googleresnet /
-densenet, ``he_initialize``, and the ``net.module.`` wrapper that gives stored
+densenet and the correlated nets correlatedclassificationconvnet / correlatedgoogleresnet, ``he_initialize``, and the ``net.module.`` wrapper that gives stored
 samples the reference's key prefix.  (The reference wraps GPU models in
 ``nn.DataParallel``; here one chain owns one GPU, so the wrapper is always the
 plain ``DummyModule`` -- the keys are identical.)
@@ -13,7 +13,8 @@ import torch
 from torch import nn
 
 from ..prior import get_prior
-from .nets import ClassificationConvNet, ClassificationDenseNet, DenseNet, ResNet
+from .nets import (ClassificationConvNet, ClassificationDenseNet, CorrelatedClassificationConvNet, CorrelatedResNet,
+                   DenseNet, ResNet)
 
 __all__ = ("get_model", "he_initialize", "DummyModule")
 
@@ -49,17 +50,21 @@ def get_model(x_train, y_train, model, width=50, depth=3, weight_prior="gaussian
     if model == "classificationdensenet":
         net = ClassificationDenseNet(x_train.size(-1), int(y_train.max()) + 1, width, depth,
                                      softmax_temp=1., **common)
-    elif model == "classificationconvnet":
+    elif model in ("classificationconvnet", "correlatedclassificationconvnet"):
         if x_train.dim() == 4:
             in_channels, img_height = x_train.shape[1], x_train.shape[-2]
         else:
             in_channels, img_height = 1, int(math.sqrt(x_train.shape[-1]))
-        net = ClassificationConvNet(in_channels, img_height, int(y_train.max()) + 1, width, depth,
-                                    softmax_temp=1., **common)
+        cls = ClassificationConvNet if model == "classificationconvnet" else CorrelatedClassificationConvNet
+        net = cls(in_channels, img_height, int(y_train.max()) + 1, width, depth, softmax_temp=1., **common)
     elif model == "googleresnet":
         # NB: conv_prior_w is not forwarded, so convolutions stay Gaussian whatever
         # weight_prior says (reference quirk, exp_utils.py:186-190).
         net = ResNet(depth=20, bn=batchnorm, softmax_temp=1., **common)
+    elif model == "correlatedgoogleresnet":
+        # weight_prior is the CONVOLUTIONS' prior, the head is Normal (exp_utils.py:201-207); weight_prior_params go to
+        # the convolutions only (the reference also hands them to the head's Normal, which raises TypeError there)
+        net = CorrelatedResNet(depth=20, bn=batchnorm, softmax_temp=1., **common)
     elif model == "densenet":
         net = DenseNet(x_train.size(-1), y_train.size(-1), width, depth, noise_std=1., **common)
     else:

@@ -3,6 +3,8 @@
 * ``ClassificationDenseNet`` -- reference ``models/dense_nets.py:16-67``
 * ``ClassificationConvNet``  -- reference ``models/conv_nets.py:18-70``
 * ``ResNet`` (googleresnet, depth 6n+2) -- reference ``models/google_resnet.py:11-78``
+* ``CorrelatedClassificationConvNet`` / ``CorrelatedResNet`` -- the same nets with a separate convolution prior
+  (reference ``models/conv_nets.py:73-115``, ``models/google_resnet.py:81-93``)
 
 Layer order, module names and prior scales follow the reference so parameter
 order (= the sampler's segment order) and ``state_dict`` keys match:
@@ -24,7 +26,7 @@ from .. import resblock as _resblock
 from .base import ClassificationModel, RegressionModel
 
 __all__ = ("Linear", "Conv2d", "LinearPrior", "Conv2dPrior", "DenseNet", "ClassificationDenseNet",
-           "ClassificationConvNet", "ResNet", "Reshape")
+           "ClassificationConvNet", "CorrelatedClassificationConvNet", "ResNet", "CorrelatedResNet", "Reshape")
 
 
 
@@ -158,6 +160,32 @@ def ClassificationConvNet(in_channels, img_height, out_features, width, depth=3,
     layers.append(nn.Flatten())
     flat = width * (img_height // 2 ** (depth - 1)) ** 2
     layers.append(LinearPrior(flat, out_features, **kw))
+    return ClassificationModel(_ConvPoolTrunk(*layers), softmax_temp)
+
+
+def CorrelatedClassificationConvNet(in_channels, img_height, out_features, width, depth=3, softmax_temp=1.,
+                                    prior_w=prior.Normal, loc_w=0., std_w=2 ** .5, prior_b=prior.Normal, loc_b=0.,
+                                    std_b=1., scaling_fn=None, weight_prior_params={}, bias_prior_params={}):
+    """``ClassificationConvNet`` whose convolutions take ``prior_w`` (e.g. ``ConvCorrelatedNormal``) and whose dense
+    head is Normal; ``weight_prior_params["lengthscale_1"]`` goes to the first convolution, ``"lengthscale_2"`` to the
+    others, the remaining entries to the head (reference: models/conv_nets.py:73-115)"""
+    assert depth >= 2, "We can't have less than two layers"
+    conv_1, conv_2 = {}, {}
+    if "lengthscale_1" in weight_prior_params:
+        conv_1["lengthscale"] = weight_prior_params["lengthscale_1"]
+    if "lengthscale_2" in weight_prior_params:
+        conv_2["lengthscale"] = weight_prior_params["lengthscale_2"]
+    dense_params = {k: v for k, v in weight_prior_params.items() if k not in ("lengthscale_1", "lengthscale_2")}
+    kw = _layer_kwargs(prior_w, loc_w, std_w, prior_b, loc_b, std_b, scaling_fn, conv_1, bias_prior_params)
+    layers = [Reshape(-1, in_channels, img_height, img_height),
+              Conv2dPrior(in_channels, width, kernel_size=3, padding=1, **kw), nn.ReLU(), nn.MaxPool2d(2)]
+    kw["weight_prior_params"] = conv_2
+    for _ in range(depth - 2):
+        layers += [Conv2dPrior(width, width, kernel_size=3, padding=1, **kw), nn.ReLU(), nn.MaxPool2d(2)]
+    layers.append(nn.Flatten())
+    flat = width * (img_height // 2 ** (depth - 1)) ** 2
+    layers.append(LinearPrior(flat, out_features, **_layer_kwargs(prior.Normal, loc_w, std_w, prior_b, loc_b, std_b,
+                                                                   scaling_fn, dense_params, bias_prior_params)))
     return ClassificationModel(_ConvPoolTrunk(*layers), softmax_temp)
 
 
@@ -361,7 +389,8 @@ class BasicBlock(nn.Module):
 
 def ResNet(softmax_temp=1., depth=20, num_classes=10, prior_w=prior.Normal, loc_w=0.,
            std_w=2 ** .5, prior_b=prior.Normal, loc_b=0., std_b=1., scaling_fn=None, bn=True,
-           weight_prior_params={}, bias_prior_params={}, conv_prior_w=prior.Normal):
+           weight_prior_params={}, bias_prior_params={}, conv_prior_w=prior.Normal, dense_prior_params=None):
+    "``dense_prior_params``: the head's weight-prior arguments, when they differ from the convolutions' (CorrelatedResNet)"
     if (depth - 2) % 6 != 0:
         raise ValueError('depth must be 6n+2 (e.g. 20, 32, 44).')
     conv_kwargs = dict(prior_w=conv_prior_w, loc_w=loc_w, std_w=std_w, prior_b=None,
@@ -380,6 +409,19 @@ def ResNet(softmax_temp=1., depth=20, num_classes=10, prior_w=prior.Normal, loc_
     layers += [nn.AvgPool2d(8), nn.Flatten(),
                LinearPrior(filters, num_classes, prior_w=prior_w, loc_w=loc_w, std_w=std_w,
                            prior_b=prior_b, loc_b=loc_b, std_b=std_b, scaling_fn=scaling_fn,
-                           weight_prior_params=weight_prior_params,
+                           weight_prior_params=(weight_prior_params if dense_prior_params is None
+                                                else dense_prior_params),
                            bias_prior_params=bias_prior_params)]
     return ClassificationModel((_BNTrunk if bn else nn.Sequential)(*layers), softmax_temp=softmax_temp)
+
+
+def CorrelatedResNet(softmax_temp=1., depth=20, num_classes=10, prior_w=prior.ConvCorrelatedNormal, loc_w=0.,
+                     std_w=2 ** .5, prior_b=prior.Normal, loc_b=0., std_b=1., scaling_fn=None, bn=True,
+                     weight_prior_params={}, bias_prior_params={}, dense_prior_w=prior.Normal):
+    """googleresnet whose convolutions take ``prior_w`` and whose dense head takes ``dense_prior_w`` (reference:
+    models/google_resnet.py:81-93).  One divergence: ``weight_prior_params`` (e.g. the lengthscale) go to the
+    convolutions only -- the reference also hands them to the head's Normal, which raises TypeError there."""
+    return ResNet(softmax_temp=softmax_temp, depth=depth, num_classes=num_classes, prior_w=dense_prior_w, loc_w=loc_w,
+                  std_w=std_w, prior_b=prior_b, loc_b=loc_b, std_b=std_b, scaling_fn=scaling_fn, bn=bn,
+                  weight_prior_params=weight_prior_params, bias_prior_params=bias_prior_params,
+                  conv_prior_w=prior_w, dense_prior_params={})

@@ -5,6 +5,7 @@ Mirrors the interface of the reference's ``bnn_priors/prior/base.py:17-87``
 models and stored ``state_dict``s keep the reference's key names
 (``<layer>.weight_prior.p`` / ``.loc`` / ``.scale`` [/ ``.df``]).
 """
+import weakref
 from numbers import Number
 
 import numpy as np
@@ -101,6 +102,38 @@ class Prior(nn.Module):
         if isinstance(extra, (Prior, nn.Parameter)) or (isinstance(extra, torch.Tensor) and extra.numel() != 1):
             return None
         return self.fused_kind, float(loc), scale_value, (float(extra) if extra is not None else 0.0)
+
+    def fused_filter_spec(self):
+        """The whitening of a multivariate prior over each convolution filter's ``P = kh * kw`` positions that the HIP
+        hook evaluates as SGMCMC_PRIOR_FILTER_WHITENED (include/sgmcmc_hip.h), computed in float64: a dict with ``P``,
+        ``base`` (_hip.FILTER_BASE_*), ``beta``, ``base_scale``, ``lognorm``, ``mu`` [P] and ``W`` [P, P] such that
+        ``log p(theta_f) = sum_k base((theta_f - mu) W)_k + lognorm``.  None when the prior is not such a family or
+        any of its arguments is learnable (prior/correlated.py)"""
+        return None
+
+    def bind_fused_filter(self, engine, index):
+        "``engine.update_filter(index, ...)`` whenever this prior's whitening changes (``refresh_fused_filter``)"
+        _FILTER_SINKS.setdefault(self, []).append((weakref.ref(engine), index))
+
+    def refresh_fused_filter(self):
+        "rewrite the device record of every sampler this prior has been fused into (in place: captured graphs follow)"
+        live = []
+        for ref, index in _FILTER_SINKS.get(self, ()):
+            eng = ref()
+            if (eng is None or getattr(eng, "filter_host", None) is None
+                    or int(eng.seg_host[index]["prior_kind"]) != 10):       # (SGMCMC_PRIOR_FILTER_WHITENED)
+                continue
+            spec = self.fused_filter_spec()
+            if spec is None:
+                raise RuntimeError("a prior fused as a filter prior no longer has a fixed whitening")
+            eng.update_filter(index, spec)
+            live.append((ref, index))
+        if self in _FILTER_SINKS:
+            _FILTER_SINKS[self] = live
+
+
+# Prior -> [(weakref to an Engine, segment index)]: where its filter record lives on the device
+_FILTER_SINKS = weakref.WeakKeyDictionary()
 
 
 def named_priors(module):

@@ -1,5 +1,8 @@
-"""Multivariate priors over a convolution filter's spatial positions (the last two dimensions of the weight), all left
-to autograd (``Potential.leftover``): none is an element-wise family of the HIP hook -- SURVEY.md section 8(f)4.
+"""Multivariate priors over a convolution filter's spatial positions (the last two dimensions of the weight).  None is an
+element-wise family of the HIP hook, but each one with FIXED arguments is a constant linear
+whitening of the filter's ``P = kh * kw`` positions followed by an element-wise base density: ``fused_filter_spec()``
+hands that whitening (computed in float64) to the hook's SGMCMC_PRIOR_FILTER_WHITENED kind.  A learnable scale or
+lengthscale (``ConvCorrNormalGamma``, ``convcorrnormal_empirical``) keeps the prior in autograd (``Potential.leftover``).
 
 * ``ConvCorrelatedNormal``: a zero-mean-shifted Gaussian over the ``kh x kw`` positions with a squared-exponential
   covariance ``scale^2 exp(-d / lengthscale)`` of their Euclidean distances, independent across channels (reference:
@@ -10,16 +13,46 @@ to autograd (``Potential.leftover``): none is an element-wise family of the HIP 
 The reference calls ``torch.cholesky`` / ``torch.symeig``, which this image's torch no longer has; ``torch.linalg.cholesky``
 and ``torch.linalg.eigh`` compute the same factors.
 """
+import math
 from numbers import Number
 
 import numpy as np
 import torch
 import torch.distributions as td
+from torch import nn
 
 from .base import Prior
 from .distributions import GeneralizedNormal
 
 __all__ = ("ConvCorrelatedNormal", "ConvCorrNormalGamma", "ConvCovariance", "FixedCovNormal", "FixedCovGenNorm")
+
+
+_LOG_2PI = float(np.log(2.0 * np.pi))
+
+
+def _fixed(v):
+    "a number or a plain tensor (not learnable, not a hyper-prior): its value in float64, else None"
+    if isinstance(v, Number):
+        return torch.tensor(float(v), dtype=torch.float64)
+    if isinstance(v, (Prior, nn.Parameter)) or not isinstance(v, torch.Tensor) or v.requires_grad:
+        return None
+    return v.detach().to("cpu", torch.float64)
+
+
+def _filter_positions(prior):
+    "P when ``p`` is a contiguous [..., kh, kw] tensor whose filters the hook can take, else None"
+    p = prior.p
+    if p.dim() < 2 or not p.is_contiguous():
+        return None
+    P = p.shape[-2] * p.shape[-1]
+    return P if 1 <= P <= 25 else None            # (SGMCMC_FILTER_MAX_P)
+
+
+def _locations(loc, P):
+    loc = _fixed(loc)
+    if loc is None or loc.numel() not in (1, P):
+        return None
+    return loc.reshape(-1).expand(P).numpy().copy()
 
 
 class SquaredExponentialNormal(td.MultivariateNormal):
@@ -48,6 +81,20 @@ class ConvCorrelatedNormal(Prior):
 
     def _draw(self, shape):
         return torch.reshape(self._dist_obj().sample(sample_shape=shape[:-2]), shape)
+
+    def fused_filter_spec(self):
+        "z = (theta_f - mu) L^-T with Sigma = L L^T = scale^2 exp(-d / lengthscale); standard normal base"
+        P = _filter_positions(self)
+        scale, ls, d = _fixed(self.scale), _fixed(self.lengthscale), _fixed(self.distance_matrix)
+        if P is None or scale is None or ls is None or d is None or scale.numel() != 1 or ls.numel() != 1:
+            return None
+        mu = _locations(self.loc, P)
+        if mu is None or d.shape != (P, P):
+            return None
+        chol = torch.linalg.cholesky(torch.exp(-d / ls) * scale ** 2)
+        W = torch.linalg.inv(chol).T
+        lognorm = -0.5 * P * _LOG_2PI - float(torch.log(torch.diagonal(chol)).sum())
+        return dict(P=P, base=0, beta=2.0, base_scale=1.0, lognorm=lognorm, mu=mu, W=W.numpy().copy())
 
 
 class ConvCorrNormalGamma(ConvCorrelatedNormal):
@@ -112,6 +159,26 @@ class ConvCovariance(Prior):
     def assign_cov(self, cov):
         for buf, new in zip((self.scale, self.inv_scale, self.log_sqrt_vals), _pca_factors(cov)):
             buf.copy_(new)
+        self.refresh_fused_filter()        # samplers that evaluate this prior in the HIP hook follow
+
+    def _base_spec(self, P):
+        "(base kind, beta, base_scale, the base density's log-normaliser over P positions) or None"
+        raise NotImplementedError
+
+    def fused_filter_spec(self):
+        """z = (theta_f - loc) inv_scale, the base density element-wise, minus log |det scale| = log_sqrt_vals ONCE PER
+        POSITION: the transformed distribution subtracts the (1, 1) log-determinant of ``_Whitening`` from every
+        element's base log-density, as the reference's (prior/conv_loc_scale.py) does -- the fixtures hold that value"""
+        P = _filter_positions(self)
+        W, lsv = _fixed(self.inv_scale), _fixed(self.log_sqrt_vals)
+        if P is None or W is None or lsv is None or W.shape != (P, P) or lsv.numel() != 1:
+            return None
+        mu, base = _locations(self.loc, P), self._base_spec(P)
+        if mu is None or base is None:
+            return None
+        kind, beta, base_scale, base_norm = base
+        return dict(P=P, base=kind, beta=beta, base_scale=base_scale, lognorm=base_norm - P * float(lsv),
+                    mu=mu, W=W.numpy().copy())
 
 
 class FixedCovNormal(ConvCovariance):
@@ -120,6 +187,9 @@ class FixedCovNormal(ConvCovariance):
 
     def _base(self, zeros):
         return td.Normal(zeros, zeros + 1)
+
+    def _base_spec(self, P):
+        return 0, 2.0, 1.0, -0.5 * P * _LOG_2PI
 
 
 class FixedCovGenNorm(ConvCovariance):
@@ -135,3 +205,11 @@ class FixedCovGenNorm(ConvCovariance):
     def _base(self, zeros, beta, base_scale):
         shape = zeros.shape
         return GeneralizedNormal(loc=zeros, scale=base_scale.expand(shape), beta=beta.expand(shape))
+
+    def _base_spec(self, P):
+        beta, s = _fixed(self.beta), _fixed(self.base_scale)
+        if beta is None or s is None or beta.numel() != 1 or s.numel() != 1:
+            return None
+        beta, s = float(beta), float(s)
+        # GeneralizedNormal: log p(z) = log beta - log(2 s) - lgamma(1 / beta) - |z / s|^beta  (prior/distributions.py)
+        return 1, beta, s, P * (np.log(beta) - np.log(2.0 * s) - math.lgamma(1.0 / beta))

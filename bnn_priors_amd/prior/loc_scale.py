@@ -105,7 +105,8 @@ def _table():
             # too) through autograd
             "gaussian_empirical": E.NormalEmpirical, "laplace_empirical": E.LaplaceEmpirical,
             "student-t_empirical": E.StudentTEmpirical, "gennorm_empirical": E.GenNormEmpirical,
-            # by name, through autograd (Potential.leftover) -- the rest of the reference's table (prior/mixture.py:17-50):
+            # by name, through autograd (Potential.leftover) -- the rest of the reference's table (prior/mixture.py:17-50);
+            # convcorrnormal(_fitted_ls) / fixedcov_* with fixed arguments through the hook's filter kind (fused_filter_spec):
             "lognormal": LogNormal, "uniform": T.Uniform, "mixture": M.Mixture, "scale_mixture": M.ScaleMixture,
             "scale_mixture_empirical": M.ScaleMixtureEmpirical, "gennorm_uniform": H.GenNormUniform,
             "convcorrnormal": C.ConvCorrelatedNormal, "convcorrnormal_fitted_ls": C.ConvCorrelatedNormal,
@@ -117,8 +118,9 @@ def _table():
 def get_prior(name):
     """Name -> class: ALL 31 names of the reference's table (prior/mixture.py:17-50).  Element-wise families, hierarchical
     scales and the learnable scales of ``gaussian_empirical`` / ``laplace_empirical`` are differentiated by the HIP prior
-    hook; everything else -- mixtures, the correlated / fixed-covariance convolution priors, the double Gamma, families
-    whose shape parameter is learnable -- is built as the reference builds it and stays in autograd
+    hook, and so are the correlated / fixed-covariance convolution priors with fixed arguments (a whitening table,
+    ``fused_filter_spec``); everything else -- mixtures, the learnable-lengthscale convolution priors, the double Gamma,
+    families whose shape parameter is learnable -- is built as the reference builds it and stays in autograd
     (``Potential.leftover``, with a one-time notice; such a model's step is not captured into a hipGraph)."""
     if isinstance(name, type) and issubclass(name, Prior):
         return name

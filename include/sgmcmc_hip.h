@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGMCMC_ABI_VERSION 6
+#define SGMCMC_ABI_VERSION 7
 #define SGMCMC_CHUNK 4096 /* default elements per arena chunk = 256 threads x 4 items x 4 elements */
 #define SGMCMC_CHUNK_SMALL 1024 /* small models: one item per thread, 4x more workgroups */
 #define SGMCMC_NSUMS 6
@@ -78,11 +78,19 @@ enum {
  *                      empirical-Bayes priors (prior/loc_scale.py:100-103 under prior/empirical_bayes.py:24-38)
  * A weight segment whose scale_link > 0 takes its scale from the VALUE of hyper segment scale_link - 1 (one element)
  * at launch time instead of prior_scale; sgmcmc_prior_grad then also adds
- * -(1/N) (d/dscale sum_j log p(theta_j)) dx/ds to the hyper segment's gradient (flags & SGMCMC_PRIOR_HAS_LINKS). */
+ * -(1/N) (d/dscale sum_j log p(theta_j)) dx/ds to the hyper segment's gradient (flags & SGMCMC_PRIOR_HAS_LINKS).
+ *
+ * FILTER_WHITENED is not element-wise: a convolution weight [Cout, Cin, kh, kw] in contiguous order is a sequence of
+ * filters of P = kh kw consecutive elements, each whitened by the segment's record L->filters[s] (prior/correlated.py):
+ *   z = (theta_f - mu) W  (row vector),  log p(theta_f) = sum_k base(z_k) + lognorm,
+ *   g_j += -(1/N) sum_k psi(z_k) W[q][k]  with q = j mod P, psi = d base / dz,
+ * base(z) = -z^2 / 2 (standard normal) or -|z / base_scale|^beta (generalised normal); their constants are in lognorm.
+ * Element j reads the other positions of its filter from theta, so it is evaluated by sgmcmc_prior_grad's full
+ * kernel only (a launch that does not write theta); prior_loc / prior_scale / prior_df are unused. */
 enum { SGMCMC_PRIOR_NONE = 0, SGMCMC_PRIOR_NORMAL = 1, SGMCMC_PRIOR_LAPLACE = 2,
        SGMCMC_PRIOR_STUDENT_T = 3, SGMCMC_PRIOR_CAUCHY = 4, SGMCMC_PRIOR_GENNORM = 5,
        SGMCMC_PRIOR_GAMMA_SOFTPLUS = 6, SGMCMC_PRIOR_UNIFORM_CDF = 7, SGMCMC_PRIOR_HALFCAUCHY_SOFTPLUS = 8,
-       SGMCMC_PRIOR_IMPROPER_SOFTPLUS = 9 };
+       SGMCMC_PRIOR_IMPROPER_SOFTPLUS = 9, SGMCMC_PRIOR_FILTER_WHITENED = 10 };
 /* flags of sgmcmc_prior_grad: some segment is linked to a hyper segment / some segment's kind is beyond CAUCHY
  * (without either the lean kernel for the four constant-scale families is launched) */
 enum { SGMCMC_PRIOR_HAS_LINKS = 1, SGMCMC_PRIOR_FULL = 2 };
@@ -99,6 +107,19 @@ typedef struct {
   int32_t scale_link;   /* > 0: the prior's scale is the value of hyper segment scale_link - 1 (see above) */
   double prior_loc, prior_scale, prior_df;
 } sgmcmc_segment;
+
+#define SGMCMC_FILTER_MAX_P 25 /* positions per filter of SGMCMC_PRIOR_FILTER_WHITENED (5 x 5) */
+enum { SGMCMC_FILTER_BASE_NORMAL = 0, SGMCMC_FILTER_BASE_GENNORM = 1 };
+/* The whitening of one FILTER_WHITENED segment (device array L->filters, one record per segment, read only for
+ * segments of that kind).  The host computes it in float64 and rewrites it in place when the covariance changes. */
+typedef struct {
+  int32_t P;          /* positions per filter, 1..SGMCMC_FILTER_MAX_P; the segment's numel is a multiple of it */
+  int32_t base;       /* SGMCMC_FILTER_BASE_* */
+  double beta, base_scale; /* generalised-normal base: base(z) = -|z / base_scale|^beta */
+  double lognorm;     /* log-normaliser of one filter's density */
+  double mu[SGMCMC_FILTER_MAX_P];                       /* location of each position */
+  double W[SGMCMC_FILTER_MAX_P * SGMCMC_FILTER_MAX_P];  /* whitening matrix, row-major with row stride P */
+} sgmcmc_filter_prior;
 
 typedef struct {
   int32_t seg;     /* owning segment */
@@ -140,6 +161,7 @@ typedef struct {
                               gradient-assembling step kernels, SGMCMC_INLINE_PRIOR) return hipErrorInvalidValue
                               when either bit is set instead of evaluating a family they do not implement */
   uint32_t reserved;
+  const sgmcmc_filter_prior* filters; /* device [n_seg] (or NULL when no segment is FILTER_WHITENED) */
 } sgmcmc_layout;
 
 /* Scalars of one transition of one parameter group, computed by the host in
@@ -245,7 +267,7 @@ int sgmcmc_segment_sum(const sgmcmc_layout* L, int which, uint32_t flags, void* 
 
 /* g <- g - (1/N) dlog p(theta)/dtheta for every segment with prior_kind != NONE
  * (element-wise Normal / Laplace / Student-t / Cauchy / generalised normal with scalar loc, scale, df / beta,
- * and the hyper-priors of hierarchical scales; see SGMCMC_PRIOR_*), i.e. what
+ * the hyper-priors of hierarchical scales and the whitened convolution filters; see SGMCMC_PRIOR_*), i.e. what
  * autograd adds for the "- log_prior / N" term of potential_avg (models/base.py:72-77,
  * prior/base.py:57-58, prior/loc_scale.py:34-35,66-67,74-77).  With calc_log_prob != 0 also
  * state[s].aux <- sum_j log p(theta_j) (fp64) and scalars[2] <- the total over segments.
