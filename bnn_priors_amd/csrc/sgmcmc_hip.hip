@@ -1581,3 +1581,5 @@ int sgmcmc_debug_normals(float* out, int64_t start, int64_t n, uint64_t seed, ui
 #endif
 #include "pool_hip.inc"
 #include "augment_hip.inc"
+// calibration / OOD-detection metrics of a posterior ensemble (evaluation side, fp64)
+#include "calib_hip.inc"

@@ -23,8 +23,8 @@ import torch
 
 from . import _capture
 
-__all__ = ("evaluate_model", "predictive_tables", "ensemble_across_chains", "ensemble_metrics",
-           "gather_samples")
+__all__ = ("evaluate_model", "evaluate_ood", "predictive_tables", "logit_tables", "ensemble_across_chains",
+           "ensemble_metrics", "gather_samples")
 
 
 def _labels_of(dataloader):
@@ -257,6 +257,15 @@ def _logits_fn(model, x):
     return g(x) if g else model.net(x)
 
 
+def _normalised_logits(model, x):
+    """the normalised logits ``model(x)`` = Categorical(logits=net(x) / T) would hold, without building the distribution
+    object (its argument validation synchronises with the host once per batch); the forward is replayed from a
+    captured graph"""
+    f = _logits_fn(model, x)
+    f = f if model.softmax_temp == 1 else f / model.softmax_temp
+    return f - f.logsumexp(dim=-1, keepdim=True)          # torch/distributions/categorical.py: logits
+
+
 @torch.no_grad()
 def predictive_tables(model, dataloader_test, samples):
     """lps [E, N] and acc_data [E, N, C] (float64, on the model's device)."""
@@ -291,12 +300,8 @@ def predictive_tables(model, dataloader_test, samples):
         for bx, by in (_row_groups(dataloader_test, device, EVAL_ROWS) if graphed and plain_temp else dataloader_test):
             bx, by = bx.to(device), by.to(device)
             if graphed and plain_temp:
-                # the numbers ``model(bx)`` = Categorical(logits=net(x) / T) would hold -- normalised logits and
-                # log p(y|x) -- without building the distribution object (its argument validation synchronises
-                # with the host once per batch); the forward itself is replayed from a captured graph
-                f = _logits_fn(model, bx)
-                f = f if model.softmax_temp == 1 else f / model.softmax_temp
-                a = f - f.logsumexp(dim=-1, keepdim=True)          # torch/distributions/categorical.py: logits
+                # the numbers ``model(bx)`` would hold -- normalised logits and log p(y|x) -- on a captured forward
+                a = _normalised_logits(model, bx)
                 lp = a.gather(-1, by.view(-1, 1)).squeeze(-1)
                 kind = "cat"
                 j = i + len(bx)
@@ -338,13 +343,65 @@ def ensemble_metrics(model, lps, acc, labels, kind):
 
 def evaluate_model(model, dataloader_test, samples, likelihood_eval=True, accuracy_eval=True,
                    calibration_eval=False):
-    if calibration_eval:
-        raise NotImplementedError("calibration metrics are outside the accelerated path")
+    """exp_utils.py:250-340.  ``calibration_eval`` adds ``ece`` / ``ace`` / ``rmsce`` of the ensemble's mean
+    probabilities (calibration.py: on the device, fp64); categorical likelihoods only, as in the reference."""
     lps, acc, labels, kind = predictive_tables(model, dataloader_test, samples)
+    if calibration_eval and (kind != "cat" or labels.dim() != 1):
+        raise ValueError(f"Cannot calculate calibration metrics for predictions of type {kind!r}")
     res = ensemble_metrics(model, lps, acc, labels, kind)
     keep = (["lp_ensemble", "lp_last"] if likelihood_eval else []) + \
            (["acc_ensemble", "acc_last"] if accuracy_eval else [])
-    return {k: res[k] for k in keep}
+    out = {k: res[k] for k in keep}
+    if calibration_eval:
+        from . import calibration
+        out.update(calibration.calibration_metrics(labels, calibration.ensemble_probs(acc).probs))
+    return out
+
+
+@torch.no_grad()
+def logit_tables(model, dataloaders, samples):
+    """The normalised logits [E, N_l, C] of every sample on each loader of ``dataloaders`` (float64, on the model's
+    device), C taken from the model's output: the loaders' labels are neither read nor needed to be in range.  Per
+    sample, one pass over each loader in turn (exp_utils.py:349-362); the model is left holding the last sample."""
+    from .models.base import ClassificationModel
+    device = next(iter(model.parameters())).device
+    E = _n_samples(samples)
+    graphed = (isinstance(model, ClassificationModel) and device.type == "cuda" and not model.training
+               and isinstance(model.softmax_temp, (int, float)))
+    tables = [None] * len(dataloaders)
+    for e in range(E):
+        model.load_state_dict({k: v[e] for k, v in samples.items()})
+        for li, loader in enumerate(dataloaders):
+            parts = []
+            for bx, _ in (_row_groups(loader, device, EVAL_ROWS) if graphed else loader):
+                bx = bx.to(device)
+                if graphed:
+                    a = _normalised_logits(model, bx)
+                else:
+                    preds = model(bx)
+                    if not isinstance(preds, torch.distributions.Categorical):
+                        raise ValueError(f"out-of-distribution scores need a categorical likelihood, not {type(preds)}")
+                    a = preds.logits
+                parts.append(a)
+            a = torch.cat(parts) if len(parts) > 1 else parts[0]
+            if tables[li] is None:
+                tables[li] = torch.empty((E,) + tuple(a.shape), dtype=torch.float64, device=device)
+            elif tables[li].shape[1:] != a.shape:
+                raise ValueError("a loader yielded a different number of rows or classes for another sample")
+            tables[li][e] = a
+    return tables
+
+
+def evaluate_ood(model, dataloader_train, dataloader_test, samples):
+    """exp_utils.py:343-380: AUROC / average precision of the ensemble's max-probability, the in-distribution set
+    ``dataloader_train`` as the positive class against the out-of-distribution set ``dataloader_test`` (whose labels
+    are ignored).  The score is max_c softmax(logsumexp_e logits - log E) in fp64, which equals the reference's
+    mean over samples of ``pred.probs`` (there averaged in float32) -- calibration.py, on the device."""
+    from . import calibration
+    acc_in, acc_out = logit_tables(model, (dataloader_train, dataloader_test), samples)
+    auroc, auprc = calibration.auroc_auprc(calibration.ensemble_probs(acc_in).conf,
+                                           calibration.ensemble_probs(acc_out).conf)
+    return {"auroc": auroc, "auprc": auprc}
 
 
 @torch.no_grad()

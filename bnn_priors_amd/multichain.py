@@ -119,6 +119,16 @@ def lanes(k, device, exclude=()):
         warnings.simplefilter("ignore")
         pool = [s for s in concurrent_streams(8, device) if s.cuda_stream not in taken]
     out = pool[:k]
+    # torch hands out streams from a fixed pool round-robin: a fresh stream can be one handed out before -- a measured
+    # one, a reserved one -- so fresh ones are drawn until their handles are new (the pool's size bounds the draws)
+    seen = taken | {s.cuda_stream for s in out}
+    for _ in range(4 * k + 64):
+        if len(out) == k:
+            break
+        s = torch.cuda.Stream(device=device)
+        if s.cuda_stream not in seen:
+            seen.add(s.cuda_stream)
+            out.append(s)
     out += [torch.cuda.Stream(device=device) for _ in range(k - len(out))]
     return out
 

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGMCMC_ABI_VERSION 7
+#define SGMCMC_ABI_VERSION 8
 #define SGMCMC_CHUNK 4096 /* default elements per arena chunk = 256 threads x 4 items x 4 elements */
 #define SGMCMC_CHUNK_SMALL 1024 /* small models: one item per thread, 4x more workgroups */
 #define SGMCMC_NSUMS 6
@@ -815,6 +815,49 @@ int sgmcmc_softmax_xent_bwd(const float* probs, const int64_t* y, const float* g
  * saved probabilities with grad_out[0] * scale == grad_scale. */
 int sgmcmc_softmax_xent_fwd_grad(const float* logits, const int64_t* y, float* loss, float* dlogits, int rows,
                                  int classes, double scale, float grad_scale, void* stream);
+
+/* ---- Calibration and out-of-distribution metrics of a posterior ensemble (evaluation, fp64, deterministic) -----------
+ * The reference computes these in numpy on the host from the [E, N, C] tables (experiments/eval_bnn.py calibration_eval /
+ * ood_eval -> exp_utils.py:323-327, 343-380, third_party/calibration_error.py).  Here the tables stay on the device and
+ * only the final scalars are read back.  Sums run in an order fixed by the sizes; counts are integers. */
+#define SGMCMC_CALIB_MAX_CLASSES 128
+#define SGMCMC_CALIB_MAX_ROWS 131072
+#define SGMCMC_CALIB_MAX_BINS 4096
+
+/* exp_utils.py:309,324 (Categorical(logits=_log_space_mean(acc_data, 0)).probs) and the max-prob / argmax of
+ * calibration_error.py:226-229: per row n of acc [samples][rows][classes] (normalised log-probabilities),
+ * lme = logsumexp_e acc[e, n, :] - log(samples) summed over e in order, probs[n, :] = softmax(lme),
+ * conf[n] = max_c probs[n, c], pred[n] = its first index (np.argmax), hit[n] = (pred[n] == labels[n]).
+ * labels and hit: both NULL or both given.  classes <= SGMCMC_CALIB_MAX_CLASSES. */
+int sgmcmc_ensemble_probs(const double* acc, const int64_t* labels, int samples, int rows, int classes, double* probs,
+                          double* conf, int64_t* pred, int64_t* hit, void* stream);
+/* The conf / pred / hit part of sgmcmc_ensemble_probs for given probabilities probs [rows][classes]. */
+int sgmcmc_row_max(const double* probs, const int64_t* labels, int rows, int classes, double* conf, int64_t* pred,
+                   int64_t* hit, void* stream);
+/* np.argsort(kind="stable") of ncols independent columns (calibration_error.py:57 np.sort, sklearn's ranking):
+ * column j's key i is keys[j * col_stride + i * elem_stride]; perm [ncols][n] (int32) receives, per column, the rows
+ * in ascending order, ties by row.  -0.0 equals 0.0; NaN sorts after every number, as in numpy.
+ * n <= SGMCMC_CALIB_MAX_ROWS.  One launch; every perm entry is written. */
+int sgmcmc_stable_order(const double* keys, int64_t elem_stride, int64_t col_stride, int n, int ncols, int32_t* perm,
+                        void* stream);
+/* GeneralCalibrationError.get_calibration_error / update_state (calibration_error.py:173-195, 197-277) on columns
+ * sorted by sgmcmc_stable_order (same keys, strides, n, ncols).  Per column j: the keys > 0; bins even (bounds:
+ * num_bins upper bounds, np.histogram_bin_edges([], num_bins, (0, 1))[1:]) or adaptive (bounds NULL: num_bins bins,
+ * upper bounds sorted[min(rint(i * (m / num_bins)), m - 1)], i = 1..num_bins-1, over the m kept keys; num_bins <= 1:
+ * one bin); np.digitize's bins; per bin the count, the score sum and the hits, where row r counts as a hit if
+ * target[r] == (class_conditional ? j : 1); err_j = sum_bins |(acc - conf) w| (l2: ((acc - conf) w)^2) with
+ * conf = S / (cnt + eps), acc = H / (cnt + eps), w = (cnt + eps) / m, eps = 2^-52; err_j = 0 if m = 0, NaN if the
+ * column holds a NaN.  col_err [ncols]: caller workspace.  out[0] = class_conditional ? sum_j err_j / ncols : err_0,
+ * square-rooted for l2.  ncols = 1 unless class_conditional. */
+int sgmcmc_calibration_error(const double* keys, int64_t elem_stride, int64_t col_stride, const int32_t* perm,
+                             const int64_t* target, int class_conditional, int n, int ncols, const double* bounds,
+                             int num_bins, int l2, double* col_err, double* out, void* stream);
+/* sklearn.metrics.roc_auc_score / average_precision_score as exp_utils.py:368-373 calls them: rows [0, n_pos) of
+ * scores are the positives (in-distribution), [n_pos, n) the negatives; perm = sgmcmc_stable_order of scores.
+ * Integer cumulative TP / FP at each distinct threshold from the top; out[0] = 2 area / (2.0 P Nn) with
+ * 2 area = sum dFP (TP_prev + TP) in integers, out[1] = sum (R_k - R_{k-1}) P_k over the thresholds in descending
+ * order, out[2] = 1 if a score is NaN (out[0], out[1] NaN then), else 0.  0 < n_pos < n. */
+int sgmcmc_rank_metrics(const double* scores, const int32_t* perm, int n, int n_pos, double* out, void* stream);
 
 /* Test hook: out[i] = spec normal (fp32) of noise index start+i. */
 int sgmcmc_debug_normals(float* out, int64_t start, int64_t n, uint64_t seed, uint32_t stream,
