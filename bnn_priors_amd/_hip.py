@@ -24,7 +24,7 @@ INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 SOURCES = [os.path.join(_HERE, "csrc", "sgmcmc_hip.hip")]
 SOURCE = SOURCES[0]
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 CHUNK = 4096
 CHUNK_SMALL = 1024
 NSUMS = 6
@@ -38,8 +38,8 @@ DEFER_FINALIZE = 256
 INLINE_PRIOR = 512
 PRIOR_NONE, PRIOR_NORMAL, PRIOR_LAPLACE, PRIOR_STUDENT_T, PRIOR_CAUCHY, PRIOR_GENNORM = 0, 1, 2, 3, 4, 5
 PRIOR_GAMMA_SOFTPLUS, PRIOR_UNIFORM_CDF, PRIOR_HALFCAUCHY_SOFTPLUS, PRIOR_IMPROPER_SOFTPLUS = 6, 7, 8, 9
-PRIOR_FILTER_WHITENED = 10
-PRIOR_HAS_LINKS, PRIOR_FULL = 1, 2
+PRIOR_FILTER_WHITENED, PRIOR_MULTIVARIATE_T = 10, 11
+PRIOR_HAS_LINKS, PRIOR_FULL, PRIOR_EVENTS = 1, 2, 4
 FILTER_MAX_P = 25
 FILTER_BASE_NORMAL, FILTER_BASE_GENNORM = 0, 1
 
@@ -55,10 +55,12 @@ CHUNK_DTYPE = np.dtype([("seg", "<i4"), ("n_valid", "<i4")], align=True)
 SEG_STATE_FIELDS = ("sum_gg", "sum_gmo", "sum_gmn", "sum_momo", "sum_mnmn", "sum_thg",
                     "delta_energy", "prev_delta", "est_temperature", "est_config_temp",
                     "point_energy", "aux")
-# sgmcmc_filter_prior: one record per segment, read for SGMCMC_PRIOR_FILTER_WHITENED segments only
+# sgmcmc_filter_prior: one record per segment, read for SGMCMC_PRIOR_FILTER_WHITENED / _MULTIVARIATE_T segments only
 FILTER_DTYPE = np.dtype([("P", "<i4"), ("base", "<i4"), ("beta", "<f8"), ("base_scale", "<f8"), ("lognorm", "<f8"),
-                         ("mu", "<f8", (FILTER_MAX_P,)), ("W", "<f8", (FILTER_MAX_P * FILTER_MAX_P,))], align=True)
-assert SEGMENT_DTYPE.itemsize == 80 and CHUNK_DTYPE.itemsize == 8 and FILTER_DTYPE.itemsize == 5232
+                         ("mu", "<f8", (FILTER_MAX_P,)), ("W", "<f8", (FILTER_MAX_P * FILTER_MAX_P,)),
+                         ("df", "<f8"), ("ev_size", "<i8"), ("ev_div", "<i8"), ("ev_mod", "<i8"), ("ev_sum", "<u8")],
+                        align=True)
+assert SEGMENT_DTYPE.itemsize == 80 and CHUNK_DTYPE.itemsize == 8 and FILTER_DTYPE.itemsize == 5272
 
 
 class Layout(ctypes.Structure):

@@ -1082,17 +1082,22 @@ __device__ __forceinline__ double prior_log_norm(const sgmcmc_segment& s, double
 // -(1/N) sum_k psi(z_k) W[q][k] to g[j] -- everything in fp64, one rounding into g.  The log-density partial is
 // base(z_q) + lognorm / P, so the P elements of a filter together carry its whole log-density.  W and mu are staged in
 // LDS (uniform reads); the P values of the filter live in registers (P <= SGMCMC_FILTER_MAX_P).
-template <typename T>
-__device__ __forceinline__ void filter_prior_chunk(const sgmcmc_layout& L, const ChunkCtx& cx,
-                                                   const sgmcmc_segment* __restrict__ sp, double num_data,
-                                                   bool calc_logp, double& lp) {
-  constexpr int kMaxP = SGMCMC_FILTER_MAX_P;
-  __shared__ double sW[kMaxP * kMaxP], smu[kMaxP];
-  const sgmcmc_filter_prior* __restrict__ fp = L.filters + cx.seg;
+// (sW [SGMCMC_FILTER_MAX_P^2] and smu [SGMCMC_FILTER_MAX_P] are the caller's LDS, shared with the multivariate-t branch)
+__device__ __forceinline__ void stage_whitening(const sgmcmc_filter_prior* __restrict__ fp, double* sW, double* smu) {
   const int P = fp->P;
   for (int i = threadIdx.x; i < P * P; i += kThreads) sW[i] = fp->W[i];
   if (threadIdx.x < P) smu[threadIdx.x] = fp->mu[threadIdx.x];
   __syncthreads();
+}
+
+template <typename T>
+__device__ __forceinline__ void filter_prior_chunk(const sgmcmc_layout& L, const ChunkCtx& cx,
+                                                   const sgmcmc_segment* __restrict__ sp, double num_data,
+                                                   bool calc_logp, double& lp, double* sW, double* smu) {
+  constexpr int kMaxP = SGMCMC_FILTER_MAX_P;
+  const sgmcmc_filter_prior* __restrict__ fp = L.filters + cx.seg;
+  const int P = fp->P;
+  stage_whitening(fp, sW, smu);
   const bool gn = fp->base == SGMCMC_FILTER_BASE_GENNORM;
   const double beta = fp->beta, inv_bs = 1.0 / fp->base_scale, ln_pos = fp->lognorm / (double)P;
   const double inv_n = 1.0 / num_data;
@@ -1134,6 +1139,103 @@ __device__ __forceinline__ void filter_prior_chunk(const sgmcmc_layout& L, const
   }
 }
 
+// (d_i = theta_f[i] - mu_i of one filter)  sum_k z_k W[q][k] with z = d W, and |z|^2 -- fp64, fixed order
+template <int kMaxP>
+__device__ __forceinline__ double whitened_row(const double (&d)[kMaxP], const double* sW, int P, int q, double* zz) {
+  double gs = 0.0, ss = 0.0;
+  for (int k = 0; k < P; ++k) {
+    double z = 0.0;
+#pragma unroll
+    for (int i = 0; i < kMaxP; ++i)
+      if (i < P) z = fma(d[i], sW[i * P + k], z);
+    if (q >= 0) gs = fma(z, sW[q * P + k], gs);
+    ss = fma(z, z, ss);
+  }
+  if (zz) *zz = ss;
+  return gs;
+}
+
+// SGMCMC_PRIOR_MULTIVARIATE_T, first launch of sgmcmc_prior_grad: the kMvtEventGroups workgroups (s, y) compute
+// M_e = sum_f |(theta_f - mu) W|^2 of the events e of segment s (when it is such a segment) into its record's ev_sum.
+// Wave w of workgroup y owns the events 4 y + w, 4 y + w + 4 kMvtEventGroups, ... (one each for up to 32 events: the
+// loop is a chain of dependent loads, so the events are spread over waves rather than queued on a few); lane l sums the
+// event's filters l, l + 64, ... in order and the 64 lane sums are combined by a fixed butterfly.
+// No atomics and no dependence on timing: the same theta gives the same bits (captured replay == eager).
+// Event e's filters: run r = 0, 1, ... of ev_div consecutive elements starting at r ev_div ev_mod + e ev_div, each
+// ev_div / P filters long.
+constexpr int kMvtEventGroups = 8;
+template <typename T>
+__global__ __launch_bounds__(kThreads) void mvt_event_kernel(sgmcmc_layout L) {
+  constexpr int kMaxP = SGMCMC_FILTER_MAX_P;
+  __shared__ double sW[kMaxP * kMaxP], smu[kMaxP];
+  const sgmcmc_segment* __restrict__ sp = &L.segs[blockIdx.x];
+  if (sp->prior_kind != SGMCMC_PRIOR_MULTIVARIATE_T || sp->g == nullptr) return;     // (uniform over the workgroup)
+  const sgmcmc_filter_prior* __restrict__ fp = L.filters + blockIdx.x;
+  stage_whitening(fp, sW, smu);
+  const int P = fp->P;
+  const int64_t ev_div = fp->ev_div, ev_mod = fp->ev_mod;
+  const int64_t per_run = ev_div / P, n_filt = fp->ev_size / P, stride = ev_div * ev_mod;
+  const T* __restrict__ th = (const T*)sp->theta;
+  double* __restrict__ out = fp->ev_sum;
+  const int wave = threadIdx.x / 64, lane = threadIdx.x % 64;
+  if ((int64_t)blockIdx.y * (kThreads / 64) >= ev_mod) return;       // (after the last __syncthreads: uniform anyway)
+  for (int64_t e = (int64_t)blockIdx.y * (kThreads / 64) + wave; e < ev_mod; e += kMvtEventGroups * (kThreads / 64)) {
+    double acc = 0.0;
+    for (int64_t f = lane; f < n_filt; f += 64) {
+      const int64_t f0 = (f / per_run) * stride + e * ev_div + (f % per_run) * P;
+      double d[kMaxP];
+#pragma unroll
+      for (int i = 0; i < kMaxP; ++i)
+        if (i < P) d[i] = (double)th[f0 + i] - smu[i];
+      double ss;
+      whitened_row<kMaxP>(d, sW, P, -1, &ss);
+      acc += ss;
+    }
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
+    if (lane == 0) out[e] = acc;
+  }
+}
+
+// SGMCMC_PRIOR_MULTIVARIATE_T, in the full prior kernel after mvt_event_kernel: element j of filter f0 (q = j mod P) of
+// event e gets g_j -= (1/N) (-(df + D) / (lambda + M_e)) (z W^T)_q, all fp64, one rounding into g.  The event's first
+// element adds its whole log-density (so the segment's chunk partials hold each event exactly once).
+template <typename T>
+__device__ __forceinline__ void mvt_prior_chunk(const sgmcmc_layout& L, const ChunkCtx& cx,
+                                                const sgmcmc_segment* __restrict__ sp, double num_data,
+                                                bool calc_logp, double& lp, double* sW, double* smu) {
+  constexpr int kMaxP = SGMCMC_FILTER_MAX_P;
+  const sgmcmc_filter_prior* __restrict__ fp = L.filters + cx.seg;
+  const int P = fp->P;
+  stage_whitening(fp, sW, smu);
+  const double lam = fp->df - 2.0, c = fp->df + (double)fp->ev_size, lognorm = fp->lognorm;
+  const int64_t ev_div = fp->ev_div, ev_mod = fp->ev_mod, first_end = ev_div * ev_mod;
+  const double* __restrict__ msum = fp->ev_sum;
+  const double inv_n = 1.0 / num_data;
+  const T* __restrict__ th = (const T*)sp->theta;
+  T* __restrict__ gp = (T*)sp->g;
+  for (int it = 0; it < items_of(L); ++it) {
+    const int j0 = (it * kThreads + threadIdx.x) * 4;
+    if (j0 >= cx.n_valid) break;
+#pragma unroll 1
+    for (int l = 0; l < 4; ++l) {
+      if (j0 + l >= cx.n_valid) break;
+      const int64_t e = cx.seg_off + j0 + l;
+      const int q = (int)(e % P);
+      const int64_t f0 = e - q;
+      double d[kMaxP];
+#pragma unroll
+      for (int i = 0; i < kMaxP; ++i)
+        if (i < P) d[i] = (double)th[f0 + i] - smu[i];
+      const double gs = whitened_row<kMaxP>(d, sW, P, q, nullptr);
+      const double M = msum[(e / ev_div) % ev_mod];
+      const double coef = -c / (lam + M);
+      gp[e] = (T)((double)gp[e] - coef * gs * inv_n);
+      if (calc_logp && e < first_end && e % ev_div == 0) lp += lognorm - 0.5 * c * log1p(M / lam);
+    }
+  }
+}
+
 // FULL = false: only the constant-scale families Normal / Laplace / Student-t / Cauchy (BASELINE's configs): the
 // lean variant the host selects unless some segment has a generalised-normal, hierarchical, hyper or filter prior
 template <typename T, bool FULL>
@@ -1145,9 +1247,14 @@ __device__ __forceinline__ void prior_body(const sgmcmc_layout& L, double num_da
   const bool parts = G.gpart != nullptr;
   const bool linked = FULL && sp->scale_link > 0;
   double acc[2] = {0.0, 0.0};   // log-density partial; d/dscale of it (hierarchical scales)
-  if (FULL && sp->prior_kind == SGMCMC_PRIOR_FILTER_WHITENED) {
-    // (a segment-level branch: the record is read only here; sgmcmc_prior_grad launches this kernel for such tables)
-    if (sp->g != nullptr) filter_prior_chunk<T>(L, cx, sp, num_data, calc_logp, acc[0]);
+  if (FULL && (sp->prior_kind == SGMCMC_PRIOR_FILTER_WHITENED || sp->prior_kind == SGMCMC_PRIOR_MULTIVARIATE_T)) {
+    // (segment-level branches: the record is read only here; sgmcmc_prior_grad launches this kernel for such tables)
+    constexpr int kMaxP = SGMCMC_FILTER_MAX_P;
+    __shared__ double sW[kMaxP * kMaxP], smu[kMaxP];
+    if (sp->g != nullptr) {
+      if (sp->prior_kind == SGMCMC_PRIOR_FILTER_WHITENED) filter_prior_chunk<T>(L, cx, sp, num_data, calc_logp, acc[0], sW, smu);
+      else mvt_prior_chunk<T>(L, cx, sp, num_data, calc_logp, acc[0], sW, smu);
+    }
   } else if ((sp->prior_kind != SGMCMC_PRIOR_NONE || parts) && sp->g != nullptr) {
     T* __restrict__ gp = (T*)sp->g + cx.seg_off;
     const T* __restrict__ thp = (const T*)sp->theta + cx.seg_off;
@@ -1505,6 +1612,12 @@ int sgmcmc_prior_grad(const sgmcmc_layout* L, double num_data, int calc_log_prob
   const bool full = (flags & (SGMCMC_PRIOR_HAS_LINKS | SGMCMC_PRIOR_FULL)) != 0;
   // a filter table is only ever read by the full kernel (FILTER_WHITENED > CAUCHY sets SGMCMC_PRIOR_FULL)
   if (L->filters != nullptr && !(L->prior_flags & SGMCMC_PRIOR_FULL)) return (int)hipErrorInvalidValue;
+  if (flags & SGMCMC_PRIOR_EVENTS) {      // multivariate-t event sums first (stream order: the prior kernel reads them)
+    if (L->filters == nullptr || !full) return (int)hipErrorInvalidValue;
+    const dim3 ev_grid((unsigned)L->n_seg, (unsigned)kMvtEventGroups);
+    if (L->dtype == SGMCMC_F32) SGMCMC_LAUNCH(mvt_event_kernel<float>, ev_grid, block, 0, s, *L);
+    else SGMCMC_LAUNCH(mvt_event_kernel<double>, ev_grid, block, 0, s, *L);
+  }
   if (L->dtype == SGMCMC_F32) {
     if (full) SGMCMC_LAUNCH((prior_kernel<float, true>), grid, block, 0, s, *L, num_data, calc_log_prob, none);
     else SGMCMC_LAUNCH((prior_kernel<float, false>), grid, block, 0, s, *L, num_data, calc_log_prob, none);

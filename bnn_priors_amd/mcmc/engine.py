@@ -252,7 +252,8 @@ class Engine:
     def set_priors(self, specs, links=None, filters=None):
         """specs[i] = None or (kind, loc, scale, shape-parameter): enable the in-kernel prior gradient;
         links[i] = index of the hyper segment whose VALUE is segment i's scale (hierarchical priors), or None;
-        filters[i] = the whitening of a PRIOR_FILTER_WHITENED segment (``Prior.fused_filter_spec()``), or None"""
+        filters[i] = the whitening of a PRIOR_FILTER_WHITENED segment (``Prior.fused_filter_spec()``) or the table of a
+        PRIOR_MULTIVARIATE_T one (``Prior.fused_mvt_spec()``), or None"""
         self._set_filters(specs, filters)
         self.prior_links = False
         for i, sp in enumerate(specs):
@@ -266,6 +267,7 @@ class Engine:
                     row["scale_link"] = links[i] + 1
                     self.prior_links = True
         self.prior_max_kind = max([0] + [int(sp[0]) for sp in specs if sp is not None])
+        self.prior_events = any(sp is not None and int(sp[0]) == _hip.PRIOR_MULTIVARIATE_T for sp in specs)
         # the layout says which prior code its table needs: lean-only entry points refuse the rest (no silent
         # Student-t evaluation of a generalised normal, no NaN placeholder scale of a linked segment)
         self.layout.prior_flags = self.prior_flags()
@@ -275,6 +277,7 @@ class Engine:
         self._seg_dirty = True
 
     _filter_dev = None       # device copy of filter_host (one buffer, rewritten in place)
+    _event_sums = None       # float64 [events of all MULTIVARIATE_T segments]: per-event sums, written on the device
 
     def _set_filters(self, specs, filters):
         if filters is None or all(f is None for f in filters):
@@ -282,10 +285,20 @@ class Engine:
             self.layout.filters = None
             return
         host = np.zeros(self.n_seg, dtype=_hip.FILTER_DTYPE)
+        mvt = [i for i, f in enumerate(filters) if f is not None and int(specs[i][0]) == _hip.PRIOR_MULTIVARIATE_T]
+        n_events = sum(int(filters[i]["ev_mod"]) for i in mvt)
+        if mvt and (self._event_sums is None or self._event_sums.numel() < n_events):
+            # the events' Mahalanobis sums (scratch of sgmcmc_prior_grad); kept while large enough, so that the records'
+            # pointers into it -- and graphs captured with them -- stay valid across set_priors
+            self._event_sums = torch.zeros(n_events, dtype=torch.float64, device=self.device)
+        base = 0
         for i, f in enumerate(filters):
             if f is not None:
-                assert specs[i] is not None and int(specs[i][0]) == _hip.PRIOR_FILTER_WHITENED
+                assert specs[i] is not None and int(specs[i][0]) in (_hip.PRIOR_FILTER_WHITENED, _hip.PRIOR_MULTIVARIATE_T)
                 self._filter_row(host[i], i, f)
+                if i in mvt:
+                    self._mvt_row(host[i], i, f, self._event_sums.data_ptr() + 8 * base)
+                    base += int(f["ev_mod"])
         self.filter_host = host
         if self._filter_dev is None or self._filter_dev.numel() != host.nbytes:
             self._filter_dev = torch.empty(host.nbytes, dtype=torch.uint8, device=self.device)
@@ -298,12 +311,21 @@ class Engine:
         if not 1 <= P <= _hip.FILTER_MAX_P or W.shape != (P, P) or mu.shape != (P,) or self.params[i].numel() % P:
             raise ValueError(f"segment {i}: a filter prior needs 1 <= P <= {_hip.FILTER_MAX_P} positions, a P x P "
                              f"whitening and P locations, and a multiple of P elements (P = {P})")
-        row["P"], row["base"] = P, int(f["base"])
-        row["beta"], row["base_scale"], row["lognorm"] = float(f["beta"]), float(f["base_scale"]), float(f["lognorm"])
+        row["P"], row["base"] = P, int(f.get("base", 0))
+        row["beta"], row["base_scale"] = float(f.get("beta", 2.0)), float(f.get("base_scale", 1.0))
+        row["lognorm"] = float(f["lognorm"])
         row["mu"][:] = 0.0
         row["W"][:] = 0.0
         row["mu"][:P] = mu
         row["W"][:P * P] = W.reshape(-1)
+
+    def _mvt_row(self, row, i, f, sums_ptr):
+        P, D, div, mod, n = int(f["P"]), int(f["ev_size"]), int(f["ev_div"]), int(f["ev_mod"]), self.params[i].numel()
+        if not (float(f["df"]) > 2 and D % P == 0 and div % P == 0 and mod >= 1 and n % (div * mod) == 0
+                and D * mod == n):
+            raise ValueError(f"segment {i}: a multivariate-t prior needs df > 2 and events of whole filters that tile "
+                             f"the tensor (P = {P}, D = {D}, ev_div = {div}, ev_mod = {mod}, numel = {n})")
+        row["df"], row["ev_size"], row["ev_div"], row["ev_mod"], row["ev_sum"] = float(f["df"]), D, div, mod, sums_ptr
 
     def update_filter(self, i, f):
         """rewrite segment i's whitening in place (``ConvCovariance.assign_cov``): the device buffer keeps its
@@ -315,9 +337,11 @@ class Engine:
 
     def prior_flags(self):
         return ((_hip.PRIOR_HAS_LINKS if self.prior_links else 0)
-                | (_hip.PRIOR_FULL if self.prior_max_kind > _hip.PRIOR_CAUCHY else 0))
+                | (_hip.PRIOR_FULL if self.prior_max_kind > _hip.PRIOR_CAUCHY else 0)
+                | (_hip.PRIOR_EVENTS if self.prior_events else 0))
 
     prior_links = False      # some segment takes its scale from a hyper segment
+    prior_events = False     # some segment is PRIOR_MULTIVARIATE_T
     prior_max_kind = 0
 
     # ------------------------------------------------------------------ deferred finalize

@@ -220,11 +220,17 @@ class SGLD(torch.optim.Optimizer):
                 filters[i] = pr.fused_filter_spec()
                 if filters[i] is not None:
                     specs[i] = (_hip.PRIOR_FILTER_WHITENED, 0.0, 1.0, 0.0)
+                    continue
+                # multivariate Student-t (prior/multivariate_t.py): the same whitening plus one reduction per event,
+                # a launch of its own before the prior kernel (SGMCMC_PRIOR_MULTIVARIATE_T)
+                filters[i] = pr.fused_mvt_spec()
+                if filters[i] is not None:
+                    specs[i] = (_hip.PRIOR_MULTIVARIATE_T, 0.0, 1.0, 0.0)
         leftover = [pr for pr, sp in zip(priors, specs) if pr is not None and sp is None]
         leftover.extend(by_param.values())   # priors whose .p this optimizer does not own
         eng.set_priors(specs, links, filters)
         for i, f in enumerate(filters):
-            if f is not None:
+            if f is not None and specs[i][0] == _hip.PRIOR_FILTER_WHITENED:
                 priors[i].bind_fused_filter(eng, i)     # ConvCovariance.assign_cov rewrites the record in place
         self._hyper_params = [eng.params[h] for h in sorted(claimed)]
         self._hyper_grads = [torch.zeros_like(p) for p in self._hyper_params]

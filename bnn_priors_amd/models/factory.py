@@ -2,7 +2,8 @@
 
 Restates the on-path part of ``bnn_priors/exp_utils.py:63-69,99-105,108-234``:
 ``get_model`` for classificationdensenet / classificationconvnet / googleresnet /
-densenet and the correlated nets correlatedclassificationconvnet / correlatedgoogleresnet, ``he_initialize``, and the ``net.module.`` wrapper that gives stored
+densenet, the correlated nets correlatedclassificationconvnet / correlatedgoogleresnet and decreasing_mvt_googleresnet,
+``he_initialize``, and the ``net.module.`` wrapper that gives stored
 samples the reference's key prefix.  (The reference wraps GPU models in
 ``nn.DataParallel``; here one chain owns one GPU, so the wrapper is always the
 plain ``DummyModule`` -- the keys are identical.)
@@ -14,7 +15,7 @@ from torch import nn
 
 from ..prior import get_prior
 from .nets import (ClassificationConvNet, ClassificationDenseNet, CorrelatedClassificationConvNet, CorrelatedResNet,
-                   DenseNet, ResNet)
+                   DecreasingMVTGoogleResNet, DenseNet, ResNet)
 
 __all__ = ("get_model", "he_initialize", "DummyModule")
 
@@ -65,6 +66,9 @@ def get_model(x_train, y_train, model, width=50, depth=3, weight_prior="gaussian
         # weight_prior is the CONVOLUTIONS' prior, the head is Normal (exp_utils.py:201-207); weight_prior_params go to
         # the convolutions only (the reference also hands them to the head's Normal, which raises TypeError there)
         net = CorrelatedResNet(depth=20, bn=batchnorm, softmax_temp=1., **common)
+    elif model == "decreasing_mvt_googleresnet":
+        # weight_prior goes to the convolutions and the head; the first blocks become MultivariateT (exp_utils.py:194-200)
+        net = DecreasingMVTGoogleResNet(depth=20, bn=batchnorm, softmax_temp=1., **common)
     elif model == "densenet":
         net = DenseNet(x_train.size(-1), y_train.size(-1), width, depth, noise_std=1., **common)
     else:

@@ -5,6 +5,8 @@
 * ``ResNet`` (googleresnet, depth 6n+2) -- reference ``models/google_resnet.py:11-78``
 * ``CorrelatedClassificationConvNet`` / ``CorrelatedResNet`` -- the same nets with a separate convolution prior
   (reference ``models/conv_nets.py:73-115``, ``models/google_resnet.py:81-93``)
+* ``DecreasingMVTGoogleResNet`` -- googleresnet with multivariate-t priors whose tails get lighter with depth
+  (reference ``models/mvt_resnets.py:51-109``)
 
 Layer order, module names and prior scales follow the reference so parameter
 order (= the sampler's segment order) and ``state_dict`` keys match:
@@ -15,6 +17,7 @@ googleresnet convolutions have no bias and always use ``conv_prior_w``
 (default Normal; ``google_resnet.py:34-43``), BatchNorm affine parameters are
 sampled without a prior.
 """
+import numpy as np
 import torch
 from torch import nn
 
@@ -26,7 +29,8 @@ from .. import resblock as _resblock
 from .base import ClassificationModel, RegressionModel
 
 __all__ = ("Linear", "Conv2d", "LinearPrior", "Conv2dPrior", "DenseNet", "ClassificationDenseNet",
-           "ClassificationConvNet", "CorrelatedClassificationConvNet", "ResNet", "CorrelatedResNet", "Reshape")
+           "ClassificationConvNet", "CorrelatedClassificationConvNet", "ResNet", "CorrelatedResNet",
+           "DecreasingMVTGoogleResNet", "Reshape")
 
 
 
@@ -425,3 +429,45 @@ def CorrelatedResNet(softmax_temp=1., depth=20, num_classes=10, prior_w=prior.Co
                   std_w=std_w, prior_b=prior_b, loc_b=loc_b, std_b=std_b, scaling_fn=scaling_fn, bn=bn,
                   weight_prior_params=weight_prior_params, bias_prior_params=bias_prior_params,
                   conv_prior_w=prior_w, dense_prior_params={})
+
+
+# degrees of freedom of the decreasing-tails googleresnet per top-level Sequential index (the paper's per-depth fits,
+# reference models/mvt_resnets.py:51-109); the layers with df > MVT_MAX_DF keep their original prior
+DECREASING_MVT_DF = {0: 3.55, 3: 3.0, 4: 5.5, 5: 20.0, 6: 32.0, 7: 50.0, 8: 60.0, 9: 70.0, 10: 80.0, 11: 90.0, 14: 1000.0}
+MVT_MAX_DF = 32.0
+
+
+def DecreasingMVTGoogleResNet(softmax_temp=1., depth=20, num_classes=10, prior_w=prior.ConvCorrelatedNormal, loc_w=0.,
+                              std_w=2 ** .5, prior_b=prior.Normal, loc_b=0., std_b=1., scaling_fn=None, bn=True,
+                              weight_prior_params={}, bias_prior_params={}):
+    """googleresnet (convolutions AND head take ``prior_w``) whose priors in the first blocks -- the stem and the blocks at
+    Sequential indices 3-6, shortcut included -- become ``MultivariateT`` with the depth's degrees of freedom, location
+    ``loc_w`` and scale ``std_w / sqrt(Cin kh kw)`` (the tensor's fan-in, not ``scaling_fn``'s in_channels).  A convolution
+    weight's events are its input channels (``permute = (1, 0, 2, 3)``, ``event_dim = 3``).  With ``prior_w =
+    ConvCorrelatedNormal`` a k x k (k > 1) filter's factor is ``chol(exp(-d)) * scale`` with the lengthscale fixed at 1.
+
+    Kept from the reference: with ``ConvCorrelatedNormal`` the head is a 640-position ConvCorrelatedNormal (the HIP hook
+    takes at most 25 positions, so that configuration differentiates the head by autograd and runs eagerly)."""
+    if depth != 20:
+        raise ValueError("the decreasing-tails googleresnet has degrees of freedom for depth 20 only")
+    net = ResNet(softmax_temp=softmax_temp, depth=depth, num_classes=num_classes, prior_w=prior_w, loc_w=loc_w,
+                 std_w=std_w, prior_b=prior_b, loc_b=loc_b, std_b=std_b, scaling_fn=scaling_fn, bn=bn,
+                 weight_prior_params=weight_prior_params, bias_prior_params=bias_prior_params, conv_prior_w=prior_w)
+    modules = dict(net.named_modules())
+    for name, pr in list(prior.named_priors(net)):
+        *parent, attr = name.split(".")
+        df = DECREASING_MVT_DF[int(parent[1])]
+        if df > MVT_MAX_DF:
+            continue
+        shape = pr.p.shape
+        conv = len(shape) == 4
+        loc, scale = loc_w, std_w / shape[1:].numel() ** 0.5
+        if conv and shape[-1] != 1 and prior_w is prior.ConvCorrelatedNormal:
+            loc = torch.zeros([1]) + loc
+            pts = np.mgrid[:shape[-2], :shape[-1]].reshape(2, -1).T
+            dist = torch.tensor(np.sum((pts[:, None, :] - pts[None, :, :]) ** 2.0, 2) ** 0.5).to(loc)
+            scale = torch.linalg.cholesky(torch.exp(-dist / 1.0)) * scale
+        mvt = prior.MultivariateT(shape, loc, scale, df=df, event_dim=3 if conv else len(shape),
+                                  permute=(1, 0, 2, 3) if conv else None)
+        modules[".".join(parent)].add_module(attr, mvt)
+    return net

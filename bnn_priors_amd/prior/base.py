@@ -111,6 +111,11 @@ class Prior(nn.Module):
         any of its arguments is learnable (prior/correlated.py)"""
         return None
 
+    def fused_mvt_spec(self):
+        """The table of a multivariate Student-t prior that the HIP hook evaluates as SGMCMC_PRIOR_MULTIVARIATE_T
+        (prior/multivariate_t.py), or None"""
+        return None
+
     def bind_fused_filter(self, engine, index):
         "``engine.update_filter(index, ...)`` whenever this prior's whitening changes (``refresh_fused_filter``)"
         _FILTER_SINKS.setdefault(self, []).append((weakref.ref(engine), index))

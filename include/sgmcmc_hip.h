@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGMCMC_ABI_VERSION 8
+#define SGMCMC_ABI_VERSION 9
 #define SGMCMC_CHUNK 4096 /* default elements per arena chunk = 256 threads x 4 items x 4 elements */
 #define SGMCMC_CHUNK_SMALL 1024 /* small models: one item per thread, 4x more workgroups */
 #define SGMCMC_NSUMS 6
@@ -86,14 +86,26 @@ enum {
  *   g_j += -(1/N) sum_k psi(z_k) W[q][k]  with q = j mod P, psi = d base / dz,
  * base(z) = -z^2 / 2 (standard normal) or -|z / base_scale|^beta (generalised normal); their constants are in lognorm.
  * Element j reads the other positions of its filter from theta, so it is evaluated by sgmcmc_prior_grad's full
- * kernel only (a launch that does not write theta); prior_loc / prior_scale / prior_df are unused. */
+ * kernel only (a launch that does not write theta); prior_loc / prior_scale / prior_df are unused.
+ *
+ * MULTIVARIATE_T is not per-filter either: the multivariate Student-t of prior/multivariate_t.py (Shah et al.'s
+ * parameterisation, lambda = df - 2).  Its record L->filters[s] holds the same P-position whitening (filters of P
+ * consecutive elements, z = (theta_f - mu) W) plus an EVENT geometry: element j belongs to event (j / ev_div) % ev_mod,
+ * and one event of D = ev_size elements is a whole number of filters.  With M_e = sum over the event's filters of |z|^2,
+ *   log p(event) = lognorm - ((df + D) / 2) log(1 + M_e / lambda),
+ *   g_j += -(1/N) (-(df + D) / (lambda + M_e)) sum_k z_k W[q][k]  with q = j mod P,
+ * lognorm = lgamma((D + df)/2) - lgamma(df/2) - (D/2) log(pi lambda) - half log |det| of the event.  sgmcmc_prior_grad
+ * first writes every event's M_e to the record's ev_sum (one launch, fp64, a fixed summation order: bit-reproducible),
+ * then the full kernel applies the gradient; the event's first element (j % ev_div == 0, j < ev_div ev_mod) carries
+ * its whole log-density.  Such a table sets SGMCMC_PRIOR_EVENTS in prior_flags (and, beyond CAUCHY, PRIOR_FULL). */
 enum { SGMCMC_PRIOR_NONE = 0, SGMCMC_PRIOR_NORMAL = 1, SGMCMC_PRIOR_LAPLACE = 2,
        SGMCMC_PRIOR_STUDENT_T = 3, SGMCMC_PRIOR_CAUCHY = 4, SGMCMC_PRIOR_GENNORM = 5,
        SGMCMC_PRIOR_GAMMA_SOFTPLUS = 6, SGMCMC_PRIOR_UNIFORM_CDF = 7, SGMCMC_PRIOR_HALFCAUCHY_SOFTPLUS = 8,
-       SGMCMC_PRIOR_IMPROPER_SOFTPLUS = 9, SGMCMC_PRIOR_FILTER_WHITENED = 10 };
+       SGMCMC_PRIOR_IMPROPER_SOFTPLUS = 9, SGMCMC_PRIOR_FILTER_WHITENED = 10, SGMCMC_PRIOR_MULTIVARIATE_T = 11 };
 /* flags of sgmcmc_prior_grad: some segment is linked to a hyper segment / some segment's kind is beyond CAUCHY
- * (without either the lean kernel for the four constant-scale families is launched) */
-enum { SGMCMC_PRIOR_HAS_LINKS = 1, SGMCMC_PRIOR_FULL = 2 };
+ * (without either the lean kernel for the four constant-scale families is launched) / some segment is
+ * MULTIVARIATE_T (its per-event sums are computed first) */
+enum { SGMCMC_PRIOR_HAS_LINKS = 1, SGMCMC_PRIOR_FULL = 2, SGMCMC_PRIOR_EVENTS = 4 };
 
 /* One parameter tensor.  Device-resident array, written by the host. */
 typedef struct {
@@ -110,8 +122,9 @@ typedef struct {
 
 #define SGMCMC_FILTER_MAX_P 25 /* positions per filter of SGMCMC_PRIOR_FILTER_WHITENED (5 x 5) */
 enum { SGMCMC_FILTER_BASE_NORMAL = 0, SGMCMC_FILTER_BASE_GENNORM = 1 };
-/* The whitening of one FILTER_WHITENED segment (device array L->filters, one record per segment, read only for
- * segments of that kind).  The host computes it in float64 and rewrites it in place when the covariance changes. */
+/* The whitening of one FILTER_WHITENED or MULTIVARIATE_T segment (device array L->filters, one record per segment, read
+ * only for segments of those kinds).  The host computes it in float64 and rewrites it in place when the covariance
+ * changes. */
 typedef struct {
   int32_t P;          /* positions per filter, 1..SGMCMC_FILTER_MAX_P; the segment's numel is a multiple of it */
   int32_t base;       /* SGMCMC_FILTER_BASE_* */
@@ -119,6 +132,12 @@ typedef struct {
   double lognorm;     /* log-normaliser of one filter's density */
   double mu[SGMCMC_FILTER_MAX_P];                       /* location of each position */
   double W[SGMCMC_FILTER_MAX_P * SGMCMC_FILTER_MAX_P];  /* whitening matrix, row-major with row stride P */
+  /* MULTIVARIATE_T only (lognorm is then the log-normaliser of one EVENT) */
+  double df;          /* degrees of freedom, > 2 */
+  int64_t ev_size;    /* D: elements per event, a multiple of P */
+  int64_t ev_div, ev_mod; /* element j belongs to event (j / ev_div) % ev_mod; ev_div is a multiple of P and
+                             ev_div * ev_mod divides the segment's numel */
+  double* ev_sum;     /* device [ev_mod]: each event's Mahalanobis norm M_e, scratch written by sgmcmc_prior_grad */
 } sgmcmc_filter_prior;
 
 typedef struct {
@@ -156,12 +175,12 @@ typedef struct {
                               [2] fused log-prior total, [3] energy total of the last transition
                               (SGMCMC_SMALL_FINALIZE only), [4] minibatch loss, [5] minibatch
                               accuracy (sgmcmc_grad_reduce_prior) */
-  uint32_t prior_flags;    /* SGMCMC_PRIOR_HAS_LINKS | SGMCMC_PRIOR_FULL as they hold for THIS segment table: the
+  uint32_t prior_flags;    /* SGMCMC_PRIOR_HAS_LINKS | _FULL | _EVENTS as they hold for THIS segment table: the
                               entry points that only carry the lean prior code (sgmcmc_grad_reduce_prior, the
                               gradient-assembling step kernels, SGMCMC_INLINE_PRIOR) return hipErrorInvalidValue
                               when either bit is set instead of evaluating a family they do not implement */
   uint32_t reserved;
-  const sgmcmc_filter_prior* filters; /* device [n_seg] (or NULL when no segment is FILTER_WHITENED) */
+  const sgmcmc_filter_prior* filters; /* device [n_seg] (or NULL when no segment is FILTER_WHITENED / MULTIVARIATE_T) */
 } sgmcmc_layout;
 
 /* Scalars of one transition of one parameter group, computed by the host in
@@ -267,7 +286,8 @@ int sgmcmc_segment_sum(const sgmcmc_layout* L, int which, uint32_t flags, void* 
 
 /* g <- g - (1/N) dlog p(theta)/dtheta for every segment with prior_kind != NONE
  * (element-wise Normal / Laplace / Student-t / Cauchy / generalised normal with scalar loc, scale, df / beta,
- * the hyper-priors of hierarchical scales and the whitened convolution filters; see SGMCMC_PRIOR_*), i.e. what
+ * the hyper-priors of hierarchical scales, the whitened convolution filters and the multivariate Student-t;
+ * see SGMCMC_PRIOR_*), i.e. what
  * autograd adds for the "- log_prior / N" term of potential_avg (models/base.py:72-77,
  * prior/base.py:57-58, prior/loc_scale.py:34-35,66-67,74-77).  With calc_log_prob != 0 also
  * state[s].aux <- sum_j log p(theta_j) (fp64) and scalars[2] <- the total over segments.
