@@ -24,7 +24,7 @@ INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 SOURCES = [os.path.join(_HERE, "csrc", "sgmcmc_hip.hip")]
 SOURCE = SOURCES[0]
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 CHUNK = 4096
 CHUNK_SMALL = 1024
 NSUMS = 6
@@ -41,7 +41,7 @@ PRIOR_GAMMA_SOFTPLUS, PRIOR_UNIFORM_CDF, PRIOR_HALFCAUCHY_SOFTPLUS, PRIOR_IMPROP
 PRIOR_FILTER_WHITENED, PRIOR_MULTIVARIATE_T = 10, 11
 PRIOR_HAS_LINKS, PRIOR_FULL, PRIOR_EVENTS = 1, 2, 4
 FILTER_MAX_P = 25
-FILTER_BASE_NORMAL, FILTER_BASE_GENNORM = 0, 1
+FILTER_BASE_NORMAL, FILTER_BASE_GENNORM, FILTER_BASE_LAPLACE, FILTER_BASE_DOUBLE_GAMMA = 0, 1, 2, 3
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
                "-fhip-fp32-correctly-rounded-divide-sqrt", "-fPIC", "-shared"]

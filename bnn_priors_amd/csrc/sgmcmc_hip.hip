@@ -1080,7 +1080,8 @@ __device__ __forceinline__ double prior_log_norm(const sgmcmc_segment& s, double
 // belongs to filter f = j / P at position q = j mod P; it re-reads its filter's P values from theta (a filter straddles
 // chunk boundaries: P does not divide the chunk), whitens them, z = (theta_f - mu) W, and adds
 // -(1/N) sum_k psi(z_k) W[q][k] to g[j] -- everything in fp64, one rounding into g.  The log-density partial is
-// base(z_q) + lognorm / P, so the P elements of a filter together carry its whole log-density.  W and mu are staged in
+// base(z_q) + lognorm / P, so the P elements of a filter together carry its whole log-density.  base / psi per
+// SGMCMC_FILTER_BASE_* (include/sgmcmc_hip.h): psi = 0 at z == 0 for every base.  W and mu are staged in
 // LDS (uniform reads); the P values of the filter live in registers (P <= SGMCMC_FILTER_MAX_P).
 // (sW [SGMCMC_FILTER_MAX_P^2] and smu [SGMCMC_FILTER_MAX_P] are the caller's LDS, shared with the multivariate-t branch)
 __device__ __forceinline__ void stage_whitening(const sgmcmc_filter_prior* __restrict__ fp, double* sW, double* smu) {
@@ -1098,7 +1099,7 @@ __device__ __forceinline__ void filter_prior_chunk(const sgmcmc_layout& L, const
   const sgmcmc_filter_prior* __restrict__ fp = L.filters + cx.seg;
   const int P = fp->P;
   stage_whitening(fp, sW, smu);
-  const bool gn = fp->base == SGMCMC_FILTER_BASE_GENNORM;
+  const int base = fp->base;
   const double beta = fp->beta, inv_bs = 1.0 / fp->base_scale, ln_pos = fp->lognorm / (double)P;
   const double inv_n = 1.0 / num_data;
   const T* __restrict__ th = (const T*)sp->theta;
@@ -1123,13 +1124,28 @@ __device__ __forceinline__ void filter_prior_chunk(const sgmcmc_layout& L, const
         for (int i = 0; i < kMaxP; ++i)
           if (i < P) z = fma(d[i], sW[i * P + k], z);
         double psi, b = 0.0;
-        if (gn) {
-          const double a = fabs(z) * inv_bs;
-          psi = z == 0.0 ? 0.0 : -copysign(beta * inv_bs * pow_noinline(a, beta - 1.0), z);
-          if (calc_logp && k == q) b = -pow_noinline(a, beta);
-        } else {
-          psi = -z;
-          b = -0.5 * z * z;
+        switch (base) {
+          case SGMCMC_FILTER_BASE_NORMAL:
+            psi = -z;
+            b = -0.5 * z * z;
+            break;
+          case SGMCMC_FILTER_BASE_GENNORM: {
+            const double a = fabs(z) * inv_bs;
+            psi = z == 0.0 ? 0.0 : -copysign(beta * inv_bs * pow_noinline(a, beta - 1.0), z);
+            if (calc_logp && k == q) b = -pow_noinline(a, beta);
+            break;
+          }
+          case SGMCMC_FILTER_BASE_LAPLACE:        // b = base_scale
+            psi = z == 0.0 ? 0.0 : -copysign(inv_bs, z);
+            b = -fabs(z) * inv_bs;
+            break;
+          case SGMCMC_FILTER_BASE_DOUBLE_GAMMA:   // c = beta, rate = 1 / base_scale
+            psi = z == 0.0 ? 0.0 : (beta - 1.0) / z - copysign(inv_bs, z);
+            // (beta - 1) log|z| as torch's xlogy: 0 when beta == 1, +-inf at z == 0 otherwise
+            if (calc_logp && k == q) b = (beta == 1.0 ? 0.0 : (beta - 1.0) * log(fabs(z))) - fabs(z) * inv_bs;
+            break;
+          default:                                // unknown base: poison, never a silent Normal
+            psi = b = __builtin_nan("");
         }
         gs = fma(psi, sW[q * P + k], gs);
         if (calc_logp && k == q) lp += b + ln_pos;

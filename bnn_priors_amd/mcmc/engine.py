@@ -311,7 +311,11 @@ class Engine:
         if not 1 <= P <= _hip.FILTER_MAX_P or W.shape != (P, P) or mu.shape != (P,) or self.params[i].numel() % P:
             raise ValueError(f"segment {i}: a filter prior needs 1 <= P <= {_hip.FILTER_MAX_P} positions, a P x P "
                              f"whitening and P locations, and a multiple of P elements (P = {P})")
-        row["P"], row["base"] = P, int(f.get("base", 0))
+        base = int(f.get("base", _hip.FILTER_BASE_NORMAL))
+        if base not in (_hip.FILTER_BASE_NORMAL, _hip.FILTER_BASE_GENNORM, _hip.FILTER_BASE_LAPLACE,
+                        _hip.FILTER_BASE_DOUBLE_GAMMA):
+            raise ValueError(f"segment {i}: unknown filter base density {base}")
+        row["P"], row["base"] = P, base
         row["beta"], row["base_scale"] = float(f.get("beta", 2.0)), float(f.get("base_scale", 1.0))
         row["lognorm"] = float(f["lognorm"])
         row["mu"][:] = 0.0

@@ -2,8 +2,8 @@
 
 Restates the on-path part of ``bnn_priors/exp_utils.py:63-69,99-105,108-234``:
 ``get_model`` for classificationdensenet / classificationconvnet / googleresnet /
-densenet, the correlated nets correlatedclassificationconvnet / correlatedgoogleresnet and decreasing_mvt_googleresnet,
-``he_initialize``, and the ``net.module.`` wrapper that gives stored
+densenet, the correlated nets correlatedclassificationconvnet / correlatedgoogleresnet, decreasing_mvt_googleresnet and
+the data-driven MNIST convnets datadrivengaussconv / datadrivendoublegammaconv, ``he_initialize``, and the ``net.module.`` wrapper that gives stored
 samples the reference's key prefix.  (The reference wraps GPU models in
 ``nn.DataParallel``; here one chain owns one GPU, so the wrapper is always the
 plain ``DummyModule`` -- the keys are identical.)
@@ -14,6 +14,7 @@ import torch
 from torch import nn
 
 from ..prior import get_prior
+from .data_driven import DataDrivenDoubleGammaClassificationConvNet, DataDrivenGaussianClassificationConvNet
 from .nets import (ClassificationConvNet, ClassificationDenseNet, CorrelatedClassificationConvNet, CorrelatedResNet,
                    DecreasingMVTGoogleResNet, DenseNet, ResNet)
 
@@ -41,7 +42,10 @@ def he_initialize(model):
 
 def get_model(x_train, y_train, model, width=50, depth=3, weight_prior="gaussian", weight_loc=0.,
               weight_scale=2 ** .5, bias_prior="gaussian", bias_loc=0., bias_scale=1.,
-              batchnorm=True, weight_prior_params={}, bias_prior_params={}):
+              batchnorm=True, weight_prior_params={}, bias_prior_params={}, *, prior_data=None):
+    """``prior_data``: the fitted tables of datadrivengaussconv / datadrivendoublegammaconv (models/data_driven.py: a
+    directory holding the reference's two data files, a mapping of their contents, or None for the installed reference
+    package's copies); unused by the other models"""
     scaling_fn = (lambda std, dim: std / dim) if weight_prior == "cauchy" \
         else (lambda std, dim: std / dim ** 0.5)
     common = dict(prior_w=get_prior(weight_prior), loc_w=weight_loc, std_w=weight_scale,
@@ -51,13 +55,23 @@ def get_model(x_train, y_train, model, width=50, depth=3, weight_prior="gaussian
     if model == "classificationdensenet":
         net = ClassificationDenseNet(x_train.size(-1), int(y_train.max()) + 1, width, depth,
                                      softmax_temp=1., **common)
-    elif model in ("classificationconvnet", "correlatedclassificationconvnet"):
+    elif model in ("classificationconvnet", "correlatedclassificationconvnet", "datadrivengaussconv",
+                   "datadrivendoublegammaconv"):
         if x_train.dim() == 4:
             in_channels, img_height = x_train.shape[1], x_train.shape[-2]
         else:
             in_channels, img_height = 1, int(math.sqrt(x_train.shape[-1]))
-        cls = ClassificationConvNet if model == "classificationconvnet" else CorrelatedClassificationConvNet
-        net = cls(in_channels, img_height, int(y_train.max()) + 1, width, depth, softmax_temp=1., **common)
+        extra = {}
+        if model == "classificationconvnet":
+            cls = ClassificationConvNet
+        elif model == "correlatedclassificationconvnet":
+            cls = CorrelatedClassificationConvNet
+        else:
+            # the fitted priors replace weight_prior / weight_scale / scaling_fn (exp_utils.py:130-152)
+            cls = (DataDrivenGaussianClassificationConvNet if model == "datadrivengaussconv"
+                   else DataDrivenDoubleGammaClassificationConvNet)
+            extra["prior_data"] = prior_data
+        net = cls(in_channels, img_height, int(y_train.max()) + 1, width, depth, softmax_temp=1., **common, **extra)
     elif model == "googleresnet":
         # NB: conv_prior_w is not forwarded, so convolutions stay Gaussian whatever
         # weight_prior says (reference quirk, exp_utils.py:186-190).

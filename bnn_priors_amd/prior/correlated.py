@@ -8,8 +8,8 @@ lengthscale (``ConvCorrNormalGamma``, ``convcorrnormal_empirical``) keeps the pr
   covariance ``scale^2 exp(-d / lengthscale)`` of their Euclidean distances, independent across channels (reference:
   bnn_priors/prior/loc_scale.py:13-63); ``ConvCorrNormalGamma``: Gamma hyper-priors on scale and lengthscale
   (prior/hierarchical.py:32-39).
-* ``FixedCovNormal`` / ``FixedCovGenNorm``: an element-wise base density pushed through the PCA transform of a given
-  covariance of the positions (prior/conv_loc_scale.py:16-140).
+* ``FixedCovNormal`` / ``FixedCovLaplace`` / ``FixedCovDoubleGamma`` / ``FixedCovGenNorm``: an element-wise base density
+  pushed through the PCA transform of a given covariance of the positions (prior/conv_loc_scale.py:16-140).
 The reference calls ``torch.cholesky`` / ``torch.symeig``, which this image's torch no longer has; ``torch.linalg.cholesky``
 and ``torch.linalg.eigh`` compute the same factors.
 """
@@ -22,12 +22,14 @@ import torch.distributions as td
 from torch import nn
 
 from .base import Prior
-from .distributions import GeneralizedNormal
+from .distributions import DoubleGamma, GeneralizedNormal
 
-__all__ = ("ConvCorrelatedNormal", "ConvCorrNormalGamma", "ConvCovariance", "FixedCovNormal", "FixedCovGenNorm")
+__all__ = ("ConvCorrelatedNormal", "ConvCorrNormalGamma", "ConvCovariance", "FixedCovNormal", "FixedCovLaplace",
+           "FixedCovDoubleGamma", "FixedCovGenNorm")
 
 
 _LOG_2PI = float(np.log(2.0 * np.pi))
+_FILTER_BASE_LAPLACE, _FILTER_BASE_DOUBLE_GAMMA = 2, 3        # (_hip.FILTER_BASE_*: the package imports without the library)
 
 
 def _fixed(v):
@@ -190,6 +192,52 @@ class FixedCovNormal(ConvCovariance):
 
     def _base_spec(self, P):
         return 0, 2.0, 1.0, -0.5 * P * _LOG_2PI
+
+
+class FixedCovLaplace(ConvCovariance):
+    "Laplace base of scale ``base_scale`` (the default sqrt(1/2) gives it unit variance)"
+
+    def __init__(self, shape, loc, cov, base_scale=math.sqrt(1 / 2)):
+        super().__init__(shape, loc, cov, base_scale=base_scale)
+
+    def _base(self, zeros, base_scale):
+        return td.Laplace(loc=zeros, scale=base_scale.expand(zeros.shape))
+
+    def _base_spec(self, P):
+        s = _fixed(self.base_scale)
+        if s is None or s.numel() != 1:
+            return None
+        s = float(s)
+        # td.Laplace: log p(z) = -log(2 s) - |z| / s
+        return _FILTER_BASE_LAPLACE, 1.0, s, -P * np.log(2.0 * s)
+
+
+class FixedCovDoubleGamma(ConvCovariance):
+    """double-Gamma base ``DoubleGamma(concentration, base_rate)``: |z| ~ Gamma(c, rate), a random sign.  Without
+    ``base_scale`` the rate is sqrt(c (1 + c)), which gives the base unit variance; else it is 1 / base_scale.
+
+    In the HIP hook the base's gradient is 0 at z == 0 (autograd gives NaN there) and its log term (c - 1) log|z| follows
+    torch's xlogy: 0 when c == 1, +-inf otherwise."""
+
+    def __init__(self, shape, loc, cov, concentration, base_scale=None):
+        if base_scale is None:
+            base_rate = (concentration * (1 + concentration)) ** .5
+        else:
+            base_rate = 1. / base_scale
+        super().__init__(shape, loc, cov, concentration=concentration, base_rate=base_rate)
+
+    def _base(self, zeros, concentration, base_rate):
+        shape = zeros.shape
+        return DoubleGamma(concentration.expand(shape), rate=base_rate.expand(shape))
+
+    def _base_spec(self, P):
+        c, r = _fixed(self.concentration), _fixed(self.base_rate)
+        if c is None or r is None or c.numel() != 1 or r.numel() != 1:
+            return None
+        c, r = float(c), float(r)
+        # DoubleGamma: log p(z) = c log r - lgamma(c) - log 2 + (c - 1) log|z| - r |z|  (prior/distributions.py); the
+        # record's beta is c and its base_scale 1 / r
+        return _FILTER_BASE_DOUBLE_GAMMA, c, 1.0 / r, P * (c * np.log(r) - math.lgamma(c) - np.log(2.0))
 
 
 class FixedCovGenNorm(ConvCovariance):

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGMCMC_ABI_VERSION 9
+#define SGMCMC_ABI_VERSION 10
 #define SGMCMC_CHUNK 4096 /* default elements per arena chunk = 256 threads x 4 items x 4 elements */
 #define SGMCMC_CHUNK_SMALL 1024 /* small models: one item per thread, 4x more workgroups */
 #define SGMCMC_NSUMS 6
@@ -84,7 +84,13 @@ enum {
  * filters of P = kh kw consecutive elements, each whitened by the segment's record L->filters[s] (prior/correlated.py):
  *   z = (theta_f - mu) W  (row vector),  log p(theta_f) = sum_k base(z_k) + lognorm,
  *   g_j += -(1/N) sum_k psi(z_k) W[q][k]  with q = j mod P, psi = d base / dz,
- * base(z) = -z^2 / 2 (standard normal) or -|z / base_scale|^beta (generalised normal); their constants are in lognorm.
+ * with the base density chosen by the record's base (SGMCMC_FILTER_BASE_*; their constants are in lognorm):
+ *   NORMAL        base(z) = -z^2 / 2                              (beta, base_scale unused)
+ *   GENNORM       base(z) = -|z / base_scale|^beta                (beta = shape, base_scale = scale)
+ *   LAPLACE       base(z) = -|z| / base_scale                     (base_scale = b; beta unused)
+ *   DOUBLE_GAMMA  base(z) = (beta - 1) log|z| - |z| / base_scale  (beta = concentration c, base_scale = 1 / rate)
+ * psi is 0 at z == 0 for every base (where autograd of GENNORM / DOUBLE_GAMMA gives NaN); the DOUBLE_GAMMA log term there
+ * follows torch's xlogy: 0 when c == 1, +-inf otherwise.  Any other base value yields NaN (never a silent Normal).
  * Element j reads the other positions of its filter from theta, so it is evaluated by sgmcmc_prior_grad's full
  * kernel only (a launch that does not write theta); prior_loc / prior_scale / prior_df are unused.
  *
@@ -121,14 +127,15 @@ typedef struct {
 } sgmcmc_segment;
 
 #define SGMCMC_FILTER_MAX_P 25 /* positions per filter of SGMCMC_PRIOR_FILTER_WHITENED (5 x 5) */
-enum { SGMCMC_FILTER_BASE_NORMAL = 0, SGMCMC_FILTER_BASE_GENNORM = 1 };
+enum { SGMCMC_FILTER_BASE_NORMAL = 0, SGMCMC_FILTER_BASE_GENNORM = 1, SGMCMC_FILTER_BASE_LAPLACE = 2,
+       SGMCMC_FILTER_BASE_DOUBLE_GAMMA = 3 };
 /* The whitening of one FILTER_WHITENED or MULTIVARIATE_T segment (device array L->filters, one record per segment, read
  * only for segments of those kinds).  The host computes it in float64 and rewrites it in place when the covariance
  * changes. */
 typedef struct {
   int32_t P;          /* positions per filter, 1..SGMCMC_FILTER_MAX_P; the segment's numel is a multiple of it */
   int32_t base;       /* SGMCMC_FILTER_BASE_* */
-  double beta, base_scale; /* generalised-normal base: base(z) = -|z / base_scale|^beta */
+  double beta, base_scale; /* the base's shape and scale (see FILTER_WHITENED above; NORMAL uses neither) */
   double lognorm;     /* log-normaliser of one filter's density */
   double mu[SGMCMC_FILTER_MAX_P];                       /* location of each position */
   double W[SGMCMC_FILTER_MAX_P * SGMCMC_FILTER_MAX_P];  /* whitening matrix, row-major with row stride P */
