@@ -24,7 +24,7 @@ INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 SOURCES = [os.path.join(_HERE, "csrc", "sgmcmc_hip.hip")]
 SOURCE = SOURCES[0]
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 CHUNK = 4096
 CHUNK_SMALL = 1024
 NSUMS = 6
@@ -40,6 +40,7 @@ PRIOR_NONE, PRIOR_NORMAL, PRIOR_LAPLACE, PRIOR_STUDENT_T, PRIOR_CAUCHY, PRIOR_GE
 PRIOR_GAMMA_SOFTPLUS, PRIOR_UNIFORM_CDF, PRIOR_HALFCAUCHY_SOFTPLUS, PRIOR_IMPROPER_SOFTPLUS = 6, 7, 8, 9
 PRIOR_FILTER_WHITENED, PRIOR_MULTIVARIATE_T = 10, 11
 PRIOR_HAS_LINKS, PRIOR_FULL, PRIOR_EVENTS = 1, 2, 4
+RIDE_JOBS = 4
 FILTER_MAX_P = 25
 FILTER_BASE_NORMAL, FILTER_BASE_GENNORM, FILTER_BASE_LAPLACE, FILTER_BASE_DOUBLE_GAMMA = 0, 1, 2, 3
 
@@ -290,6 +291,9 @@ EXPORTS = {
                                + [ctypes.POINTER(ctypes.c_int), ctypes.c_void_p]),
     "sgmcmc_conv3x3_bwd_ex": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.POINTER(ConvBwdEpilogue)]
                               + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_int), ctypes.c_void_p]),
+    "sgmcmc_conv3x3_bwd_ride": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.POINTER(ConvBwdEpilogue)]
+                                + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 3
+                                + [ctypes.POINTER(ctypes.c_int), ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "sgmcmc_conv_down_bwd_sum_slices": (ctypes.c_int, [ctypes.c_int] * 3),
     "sgmcmc_bn_eval_fwd": (ctypes.c_int, [ctypes.c_void_p] * 6 + [ctypes.c_double] + [ctypes.c_int] * 4
                            + [ctypes.c_void_p, ctypes.c_void_p]),

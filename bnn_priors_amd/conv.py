@@ -364,7 +364,10 @@ def _both_grads(x, w, dy, defer, sums_for=None):
             _bnlink.tag_gradient(dx, partial, n_part, _bnlink.PREMASK)
         _pending.append((scratch, dw, slabs.value, 9))
         return dx, dw.view(dw.shape)
-    if sums_for is None:
+    riders = take_riders(c, hw)
+    if sums_for is None and riders is not None:       # (an empty epilogue: the launch of sgmcmc_conv3x3_bwd)
+        err = bwd_ex(lib, x, w, dy, dx, _hip.ConvBwdEpilogue(), dw, scratch, slabs if defer else None, _stream(), riders)
+    elif sums_for is None:
         err = lib.sgmcmc_conv3x3_bwd(x.data_ptr(), w.data_ptr(), dy.data_ptr(), dx.data_ptr(), dw.data_ptr(),
                                      scratch.data_ptr(), n, c, hw, ctypes.byref(slabs) if defer else None, _stream())
     else:
@@ -376,9 +379,7 @@ def _both_grads(x, w, dy, defer, sums_for=None):
                                  group_imgs=_group_imgs(n), mask_dx=int(_bnlink.PREMASK))
         from . import bn as _bn
         E.wrw_mult = WRW_GROUP_MULT and _bn.groups()
-        err = lib.sgmcmc_conv3x3_bwd_ex(x.data_ptr(), w.data_ptr(), dy.data_ptr(), dx.data_ptr(), ctypes.byref(E),
-                                        dw.data_ptr(), scratch.data_ptr(), n, c, hw,
-                                        ctypes.byref(slabs) if defer else None, _stream())
+        err = bwd_ex(lib, x, w, dy, dx, E, dw, scratch, slabs if defer else None, _stream(), riders)
         _bnlink.tag_gradient(dx, partial, n_part, _bnlink.PREMASK)
     if err:
         _hip.check(err, "sgmcmc_conv3x3_bwd")
@@ -393,6 +394,51 @@ def _both_grads(x, w, dy, defer, sums_for=None):
 # Weight-gradient slabs whose reduction waits for the end of the running backward pass, where ONE launch
 # sums all of them (autograd's final callback); see ``deferring`` above for when a call may defer.
 _pending = []
+
+
+# ---- riders: pending slab reductions inside the NEXT trunk backward launch (csrc/conv_hip.inc, RideJobs) ------------
+# Inside a deferring pass every trunk backward launch (sgmcmc_conv3x3_bwd_ex: the carrier) takes up to _hip.RIDE_JOBS
+# jobs off ``_pending`` and reduces them in a few extra workgroups of its own grid.  Enqueue order is stream order, so
+# the slabs of every pending job were written by an earlier launch: the kernel boundary is the synchronisation.  The
+# end-of-pass reduction keeps the jobs that found no carrier (the last trunk convolution's, the stem's).  Same blocks,
+# same order of additions: the gradients carry the bits of ``_flush_pending``'s route (tests/test_wrw_ride.py).
+# Module attributes, not environment switches: ``WRW_RIDE = False`` restores the single reduction at the end;
+# ``RIDE_CARRIERS`` lists the carrier shapes (channels, side) that take riders, ``RIDERS_FIRST`` puts the riders ahead of
+# the launch's own workgroups instead of behind them -- the shipped values are the measured ones (docs/lab_notes.md):
+# the 64-channel launch, two workgroups per CU and 1.25 rounds of them already, is no carrier (its jobs wait for the
+# first 32-channel launch); riders ahead of the grid delay the weight-gradient workgroups and lose most of the gain.
+WRW_RIDE = True
+RIDE_CARRIERS = {(16, 32), (32, 16)}
+RIDERS_FIRST = False
+
+
+def take_riders(c, hw):
+    """the pending jobs that ride in the (c, hw) backward launch about to be enqueued on the current stream, removed
+    from ``_pending`` -> list of (scratch, dw, slabs, taps), which the caller keeps alive until the launch is enqueued;
+    None: no riders (outside a deferring scope, route switched off, nothing pending)"""
+    if not (WRW_RIDE and _defer["active"] and not SIDE_STREAM and (c, hw) in RIDE_CARRIERS and _pending):
+        return None
+    taken = _pending[:_hip.RIDE_JOBS]
+    del _pending[:_hip.RIDE_JOBS]
+    return taken
+
+
+def _fill_jobs(jobs, entries):
+    for j, (scratch, dw, slabs, taps) in zip(jobs, entries):
+        j.part, j.out, j.n_slabs, j.numel, j.taps = scratch.data_ptr(), dw.data_ptr(), slabs, dw.numel(), taps
+    return jobs
+
+
+def bwd_ex(lib, x, w, dy, dx, E, dw, scratch, slabs, stream, riders=None):
+    """sgmcmc_conv3x3_bwd_ex, or sgmcmc_conv3x3_bwd_ride when ``riders`` (take_riders) come along; dw None / slabs (a
+    ctypes.c_int) not None: the launch's own slabs are left for a later reduction -> the error code"""
+    n, c, hw = x.shape[0], x.shape[1], x.shape[2]
+    args = (x.data_ptr(), w.data_ptr(), dy.data_ptr(), dx.data_ptr(), ctypes.byref(E), 0 if dw is None else dw.data_ptr(),
+            scratch.data_ptr(), n, c, hw, None if slabs is None else ctypes.byref(slabs))
+    if not riders:
+        return lib.sgmcmc_conv3x3_bwd_ex(*args, stream)
+    jobs = _fill_jobs((_hip.ReduceJob * len(riders))(), riders)
+    return lib.sgmcmc_conv3x3_bwd_ride(*args, ctypes.cast(jobs, ctypes.c_void_p), len(riders), int(RIDERS_FIRST), stream)
 
 
 # ---- weight gradients off the critical path (MEASURED SLOWER: off by default) ------------------------------------
@@ -441,9 +487,7 @@ def _flush_pending():
     _join_side()
     if not _pending:
         return
-    jobs = (_hip.ReduceJob * len(_pending))()
-    for j, (scratch, dw, slabs, taps) in zip(jobs, _pending):
-        j.part, j.out, j.n_slabs, j.numel, j.taps = scratch.data_ptr(), dw.data_ptr(), slabs, dw.numel(), taps
+    jobs = _fill_jobs((_hip.ReduceJob * len(_pending))(), _pending)
     err = _hip.lib().sgmcmc_wrw_reduce_many(ctypes.cast(jobs, ctypes.c_void_p), len(_pending), _stream())
     _pending.clear()
     if err:

@@ -846,30 +846,6 @@ __global__ __launch_bounds__(256) void conv3x3_wrw_kernel(const float* __restric
   conv3x3_wrw_body<C, HW, ROWS>(xcd_remap<C>((int)blockIdx.x, (int)gridDim.x), x, dy, part, n_items);
 }
 
-// (Block order: the weight-gradient blocks come FIRST.  They process two items each and run about twice as
-// long as a data-gradient block; dispatched first they overlap the data-gradient blocks instead of forming a
-// half-empty tail round -- longest-processing-time-first over the 2 x 256 resident workgroup slots.)
-// Both gradients of one convolution in ONE launch: n_dgrad blocks compute the data gradient
-// (forward body on dy with transposed + flipped weights), the rest the weight-gradient slabs.  The two
-// halves are independent, so they share the GPU instead of running back to back with a launch gap.
-// (3 waves per SIMD = 3 workgroups per CU, what the LDS footprint admits: the ADD + SUMS variant at 16 channels sat two
-// registers above that step.  At 64 channels the data gradient's 80 KB of LDS admit two workgroups per CU whatever is
-// requested: asking for three only capped the registers at 168 and made the ADD + SUMS instantiation spill: two there)
-template <int C, int HW, int ROWS, bool EPI, bool SUMS, bool MULT = false>
-__global__ __launch_bounds__(256, (MULT || C >= 64) ? 2 : 3) void conv3x3_bwd_kernel(const float* __restrict__ x,
-                                                          const float* __restrict__ w,
-                                                          const float* __restrict__ dy,
-                                                          float* __restrict__ dx, float* __restrict__ part,
-                                                          int n_dgrad, int n_items, BwdEpilogue E) {
-  const int n_wrw = (int)gridDim.x - n_dgrad;
-  const int b = (int)blockIdx.x;
-  // (both halves in image order per XCD: image i's weight-gradient items and its data-gradient tiles share dy in one L2)
-  if (b < n_wrw) {
-    conv3x3_wrw_body<C, HW, ROWS, MULT>(xcd_remap<C>(b, n_wrw), x, dy, part, n_items, E.wrw_mult);
-  }
-  else conv3x3_body<C, HW, ROWS, true, false, EPI, SUMS>(xcd_remap<C>(b - n_wrw, n_dgrad), dy, w, dx, nullptr, 0, &E);
-}
-
 // where element j of a slab lands in the output: slabs of `taps` > 1 are tap-major ([taps][E / taps]) and the
 // output is tap-minor ([E / taps][taps], i.e. [co][ci][r,s])
 __device__ __forceinline__ int slab_out_index(int j, int E, int taps) {
@@ -893,9 +869,13 @@ __host__ __device__ __forceinline__ int reduce_blocks(int P, int E) {
   return (P >= 256 && E <= 4096) ? (E + 15) / 16 : reduce_vec(P, E) ? (E + 255) / 256 : (E + 63) / 64;
 }
 
+// (sh: 4 KiB of the caller's LDS, 16-byte aligned.  DEEP: the loads in flight per round trip -- 32, or 8 for the rider
+// workgroups of conv3x3_bwd_kernel, whose register budget belongs to the convolution roles; the additions are the same
+// 4-at-a-time sequence either way: slab p + u * ng goes to running sum u % 4 in increasing u)
+template <int DEEP = 32>
 __device__ __forceinline__ void reduce_block_vec(const float* __restrict__ part, int P, int E, float* __restrict__ out,
-                                                 int taps, int blk) {
-  __shared__ float4 shv[4][64];
+                                                 int taps, int blk, float* __restrict__ sh) {
+  float4* __restrict__ shv = reinterpret_cast<float4*>(sh);      // [4][64]
   const int le = threadIdx.x & 63, pg = threadIdx.x >> 6, ng = 4;
   const int e = (blk * 64 + le) * 4;
   const bool aligned = (reinterpret_cast<uintptr_t>(part) & 15) == 0;
@@ -910,7 +890,7 @@ __device__ __forceinline__ void reduce_block_vec(const float* __restrict__ part,
     int p = pg;
     // a thread's slabs are a chain of round trips to memory: 32 (then 8) 16-byte loads in flight per trip, added in the
     // 4-at-a-time order whatever the batching (64 slabs per thread at 16 channels: 2 trips instead of 8)
-    for (; p + 31 * ng < P; p += 32 * ng) {
+    if constexpr (DEEP >= 32) for (; p + 31 * ng < P; p += 32 * ng) {
       float4 v[32];
 #pragma unroll
       for (int u = 0; u < 32; ++u) v[u] = ld(p + u * ng);
@@ -932,10 +912,10 @@ __device__ __forceinline__ void reduce_block_vec(const float* __restrict__ part,
     a = make_float4((b0.x + b1.x) + (b2.x + b3.x), (b0.y + b1.y) + (b2.y + b3.y), (b0.z + b1.z) + (b2.z + b3.z),
                     (b0.w + b1.w) + (b2.w + b3.w));
   }
-  shv[pg][le] = a;
+  shv[pg * 64 + le] = a;
   __syncthreads();
   if (pg == 0 && e < E) {
-    const float4 q0 = shv[0][le], q1 = shv[1][le], q2 = shv[2][le], q3 = shv[3][le];
+    const float4 q0 = shv[le], q1 = shv[64 + le], q2 = shv[128 + le], q3 = shv[192 + le];
     const float r[4] = {(q0.x + q1.x) + (q2.x + q3.x), (q0.y + q1.y) + (q2.y + q3.y), (q0.z + q1.z) + (q2.z + q3.z),
                         (q0.w + q1.w) + (q2.w + q3.w)};
 #pragma unroll
@@ -943,10 +923,12 @@ __device__ __forceinline__ void reduce_block_vec(const float* __restrict__ part,
   }
 }
 
+constexpr int REDUCE_LDS_FLOATS = 1024;     // what reduce_block needs of its caller's LDS
+template <int DEEP = 32>
 __device__ __forceinline__ void reduce_block(const float* __restrict__ part, int P, int E, float* __restrict__ out,
-                                             int taps, int blk) {
-  if (reduce_vec(P, E)) { reduce_block_vec(part, P, E, out, taps, blk); return; }
-  __shared__ float sh[16][16];    // normal: [4][64] in the same storage
+                                             int taps, int blk, float* __restrict__ sh) {
+  if (reduce_vec(P, E)) { reduce_block_vec<DEEP>(part, P, E, out, taps, blk, sh); return; }
+  // sh as [16][16]; normal: [4][64] in the same storage
   const bool wide = reduce_wide(P, E);
   const int ew = wide ? 16 : 64, ng = wide ? 16 : 4;
   const int le = threadIdx.x % ew, pg = threadIdx.x / ew;
@@ -971,7 +953,7 @@ __device__ __forceinline__ void reduce_block(const float* __restrict__ part, int
     for (; p < P; p += ng) b0 += part[(size_t)p * E + e];
     a = (b0 + b1) + (b2 + b3);
   }
-  float* __restrict__ shf = &sh[0][0];
+  float* __restrict__ shf = sh;
   shf[pg * ew + le] = a;
   __syncthreads();
   if (pg == 0 && e < E) {
@@ -991,7 +973,8 @@ __device__ __forceinline__ void reduce_block(const float* __restrict__ part, int
 
 __global__ __launch_bounds__(256) void wrw_reduce_kernel(const float* __restrict__ part, int P, int E,
                                                          float* __restrict__ out, int taps) {
-  reduce_block(part, P, E, out, taps, (int)blockIdx.x);
+  __shared__ __attribute__((aligned(16))) float sh[REDUCE_LDS_FLOATS];
+  reduce_block(part, P, E, out, taps, (int)blockIdx.x, sh);
 }
 
 // the same reduction for up to SGMCMC_REDUCE_JOBS weight gradients in one launch (the whole backward
@@ -1003,11 +986,65 @@ struct ReduceJobs {
 };
 
 __global__ __launch_bounds__(256) void wrw_reduce_many_kernel(ReduceJobs J) {
+  __shared__ __attribute__((aligned(16))) float sh[REDUCE_LDS_FLOATS];
   int j = 0;
   while (j + 1 < J.n && (int)blockIdx.x >= J.first_block[j + 1]) ++j;
   // identical summation order to wrw_reduce_kernel: the result does not depend on the route
   reduce_block(J.job[j].part, J.job[j].n_slabs, J.job[j].numel, J.job[j].out, J.job[j].taps,
-               (int)blockIdx.x - J.first_block[j]);
+               (int)blockIdx.x - J.first_block[j], sh);
+}
+
+// Riders: up to SGMCMC_RIDE_JOBS slab reductions of EARLIER launches (reduce_block: the blocks of wrw_reduce_many_kernel,
+// the same bits) as a third role of the merged backward launch.  Their slabs were complete when the launch that wrote
+// them ended -- the kernel boundary is the only synchronisation -- and nothing but the sampler at the end of the pass
+// reads their result, so they leave the dependent chain: a rider takes a workgroup slot that the first finished
+// weight-gradient workgroups free and waits for memory while the data-gradient workgroups compute.
+// first != 0: the riders lead the grid, padded to a multiple of 8 blocks so that the other roles keep their XCDs.
+struct RideJobs {
+  sgmcmc_reduce_job job[SGMCMC_RIDE_JOBS];
+  int first_block[SGMCMC_RIDE_JOBS + 1];
+  int n, first;
+};
+__host__ __device__ __forceinline__ int ride_blocks(const RideJobs& R) {
+  return R.first ? (R.first_block[R.n] + 7) & ~7 : R.first_block[R.n];
+}
+
+// (Block order: the weight-gradient blocks come FIRST.  They process two items each and run about twice as
+// long as a data-gradient block; dispatched first they overlap the data-gradient blocks instead of forming a
+// half-empty tail round -- longest-processing-time-first over the 2 x 256 resident workgroup slots.)
+// Both gradients of one convolution in ONE launch: n_dgrad blocks compute the data gradient
+// (forward body on dy with transposed + flipped weights), the rest the weight-gradient slabs.  The two
+// halves are independent, so they share the GPU instead of running back to back with a launch gap.
+// (3 waves per SIMD = 3 workgroups per CU, what the LDS footprint admits: the ADD + SUMS variant at 16 channels sat two
+// registers above that step.  At 64 channels the data gradient's 80 KB of LDS admit two workgroups per CU whatever is
+// requested: asking for three only capped the registers at 168 and made the ADD + SUMS instantiation spill: two there)
+template <int C, int HW, int ROWS, bool EPI, bool SUMS, bool MULT = false>
+__global__ __launch_bounds__(256, (MULT || C >= 64) ? 2 : 3) void conv3x3_bwd_kernel(const float* __restrict__ x,
+                                                          const float* __restrict__ w,
+                                                          const float* __restrict__ dy,
+                                                          float* __restrict__ dx, float* __restrict__ part,
+                                                          int n_dgrad, int n_items, BwdEpilogue E, RideJobs R) {
+  const int n_ride = ride_blocks(R);
+  const int n_wrw = (int)gridDim.x - n_dgrad - n_ride;
+  int b = (int)blockIdx.x;
+  if (n_ride) {      // (riders last: ids [n_wrw + n_dgrad, grid); first: ids [0, n_ride) -- the other roles' ids map as without)
+    const int r = R.first ? b : b - (n_wrw + n_dgrad);
+    if (R.first) b -= n_ride;
+    if (r >= 0 && r < n_ride) {
+      if (r >= R.first_block[R.n]) return;      // padding
+      extern __shared__ __attribute__((aligned(16))) float lds[];
+      int j = 0;
+      while (j + 1 < R.n && r >= R.first_block[j + 1]) ++j;
+      reduce_block<8>(R.job[j].part, R.job[j].n_slabs, R.job[j].numel, R.job[j].out, R.job[j].taps, r - R.first_block[j],
+                      lds);
+      return;
+    }
+  }
+  // (both halves in image order per XCD: image i's weight-gradient items and its data-gradient tiles share dy in one L2)
+  if (b < n_wrw) {
+    conv3x3_wrw_body<C, HW, ROWS, MULT>(xcd_remap<C>(b, n_wrw), x, dy, part, n_items, E.wrw_mult);
+  }
+  else conv3x3_body<C, HW, ROWS, true, false, EPI, SUMS>(xcd_remap<C>(b - n_wrw, n_dgrad), dy, w, dx, nullptr, 0, &E);
 }
 
 template <int C, int HW, int ROWS>
@@ -1033,7 +1070,8 @@ template <int C, int HW, int ROWS>
 // only -- the two halves are independent, so a caller may also put them on two streams: the weight gradient then
 // leaves the backward pass's critical path (sgmcmc_conv3x3_bwd_part, a measured alternative)
 int launch_bwd(const float* x, const float* w, const float* dy, float* dx, float* dw, float* part, int n_img,
-               int* n_slabs, hipStream_t s, const BwdEpilogue& E = BwdEpilogue{}, int which = 0) {
+               int* n_slabs, hipStream_t s, const BwdEpilogue& E = BwdEpilogue{}, int which = 0,
+               const RideJobs& R = RideJobs{}) {
   using G = WrwCfg<C, HW, ROWS>;
   using F = Cfg<C, HW, ROWS>;
   const int mult = (E.wrw_mult > 1 && E.s_partial != nullptr) ? E.wrw_mult : 1;
@@ -1060,14 +1098,15 @@ int launch_bwd(const float* x, const float* w, const float* dy, float* dx, float
   BwdEpilogue Ev = E;
   Ev.n_slices = n_img * F::BANDS;
   Ev.wrw_mult = mult;
-  const dim3 grid((unsigned)(n_dgrad + n_wrw));
+  static_assert(F::LDS_BYTES >= REDUCE_LDS_FLOATS * sizeof(float), "the riders reduce in the launch's LDS");
+  const dim3 grid((unsigned)(n_dgrad + n_wrw + ride_blocks(R)));
   const bool epi = E.e_dout != nullptr, sums = E.s_partial != nullptr;
-  if (mult > 1 && epi) SGMCMC_LAUNCH(m11, grid, dim3(256), lds, s, x, w, dy, dx, part, n_dgrad, n_items, Ev);
-  else if (mult > 1) SGMCMC_LAUNCH(m01, grid, dim3(256), lds, s, x, w, dy, dx, part, n_dgrad, n_items, Ev);
-  else if (epi && sums) SGMCMC_LAUNCH(k11, grid, dim3(256), lds, s, x, w, dy, dx, part, n_dgrad, n_items, Ev);
-  else if (epi) SGMCMC_LAUNCH(k10, grid, dim3(256), lds, s, x, w, dy, dx, part, n_dgrad, n_items, Ev);
-  else if (sums) SGMCMC_LAUNCH(k01, grid, dim3(256), lds, s, x, w, dy, dx, part, n_dgrad, n_items, Ev);
-  else SGMCMC_LAUNCH(k00, grid, dim3(256), lds, s, x, w, dy, dx, part, n_dgrad, n_items, Ev);
+  if (mult > 1 && epi) SGMCMC_LAUNCH(m11, grid, dim3(256), lds, s, x, w, dy, dx, part, n_dgrad, n_items, Ev, R);
+  else if (mult > 1) SGMCMC_LAUNCH(m01, grid, dim3(256), lds, s, x, w, dy, dx, part, n_dgrad, n_items, Ev, R);
+  else if (epi && sums) SGMCMC_LAUNCH(k11, grid, dim3(256), lds, s, x, w, dy, dx, part, n_dgrad, n_items, Ev, R);
+  else if (epi) SGMCMC_LAUNCH(k10, grid, dim3(256), lds, s, x, w, dy, dx, part, n_dgrad, n_items, Ev, R);
+  else if (sums) SGMCMC_LAUNCH(k01, grid, dim3(256), lds, s, x, w, dy, dx, part, n_dgrad, n_items, Ev, R);
+  else SGMCMC_LAUNCH(k00, grid, dim3(256), lds, s, x, w, dy, dx, part, n_dgrad, n_items, Ev, R);
   if (which == 1) return (int)hipGetLastError();        // no slabs were written
   if (n_slabs) {  // the caller reduces the slabs later (sgmcmc_wrw_reduce_many)
     *n_slabs = P;
@@ -1097,10 +1136,10 @@ extern "C" int sgmcmc_conv3x3_bwd(const float* x, const float* w, const float* d
 
 static int conv3x3_bwd_with(const float* x, const float* w, const float* dy, float* dx, float* dw, float* scratch,
                             int n_img, int channels, int hw, int* d, hipStream_t s, const conv::BwdEpilogue& E,
-                            int which = 0) {
-  if (channels == 16 && hw == 32) return conv::launch_bwd<16, 32, 8>(x, w, dy, dx, dw, scratch, n_img, d, s, E, which);
-  if (channels == 32 && hw == 16) return conv::launch_bwd<32, 16, 8>(x, w, dy, dx, dw, scratch, n_img, d, s, E, which);
-  if (channels == 64 && hw == 8) return conv::launch_bwd<64, 8, 8>(x, w, dy, dx, dw, scratch, n_img, d, s, E, which);
+                            int which = 0, const conv::RideJobs& R = conv::RideJobs{}) {
+  if (channels == 16 && hw == 32) return conv::launch_bwd<16, 32, 8>(x, w, dy, dx, dw, scratch, n_img, d, s, E, which, R);
+  if (channels == 32 && hw == 16) return conv::launch_bwd<32, 16, 8>(x, w, dy, dx, dw, scratch, n_img, d, s, E, which, R);
+  if (channels == 64 && hw == 8) return conv::launch_bwd<64, 8, 8>(x, w, dy, dx, dw, scratch, n_img, d, s, E, which, R);
   return (int)hipErrorInvalidValue;
 }
 
@@ -1115,10 +1154,9 @@ extern "C" int sgmcmc_conv3x3_bwd_add(const float* x, const float* w, const floa
   return conv3x3_bwd_with(x, w, dy, dx, dw, scratch, n_img, channels, hw, deferred_slabs, (hipStream_t)stream, E);
 }
 
-extern "C" int sgmcmc_conv3x3_bwd_ex(const float* x, const float* w, const float* dy, float* dx,
-                                     const sgmcmc_conv_bwd_epilogue* epi, float* dw, float* scratch, int n_img,
-                                     int channels, int hw, int* deferred_slabs, void* stream) {
-  SGMCMC_FRESH_ERROR_STATE();
+static int conv3x3_bwd_ex_with(const float* x, const float* w, const float* dy, float* dx,
+                               const sgmcmc_conv_bwd_epilogue* epi, float* dw, float* scratch, int n_img, int channels,
+                               int hw, int* deferred_slabs, void* stream, const conv::RideJobs& R) {
   if (!x || !w || !dy || !dx || !epi || !scratch || n_img <= 0 || (!dw && !deferred_slabs))
     return (int)hipErrorInvalidValue;
   if (epi->e_out && !epi->e_dout) return (int)hipErrorInvalidValue;      // (e_dout alone: added unmasked)
@@ -1136,7 +1174,36 @@ extern "C" int sgmcmc_conv3x3_bwd_ex(const float* x, const float* w, const float
     if (epi->group_imgs < 0 || (epi->group_imgs > 0 && n_img % epi->group_imgs)) return (int)hipErrorInvalidValue;
     conv::set_groups(E, epi->group_imgs);
   }
-  return conv3x3_bwd_with(x, w, dy, dx, dw, scratch, n_img, channels, hw, deferred_slabs, (hipStream_t)stream, E);
+  return conv3x3_bwd_with(x, w, dy, dx, dw, scratch, n_img, channels, hw, deferred_slabs, (hipStream_t)stream, E, 0, R);
+}
+
+extern "C" int sgmcmc_conv3x3_bwd_ex(const float* x, const float* w, const float* dy, float* dx,
+                                     const sgmcmc_conv_bwd_epilogue* epi, float* dw, float* scratch, int n_img,
+                                     int channels, int hw, int* deferred_slabs, void* stream) {
+  SGMCMC_FRESH_ERROR_STATE();
+  return conv3x3_bwd_ex_with(x, w, dy, dx, epi, dw, scratch, n_img, channels, hw, deferred_slabs, stream, conv::RideJobs{});
+}
+
+// ... with up to SGMCMC_RIDE_JOBS slab reductions of earlier launches riding in the grid (conv::RideJobs)
+extern "C" int sgmcmc_conv3x3_bwd_ride(const float* x, const float* w, const float* dy, float* dx,
+                                       const sgmcmc_conv_bwd_epilogue* epi, float* dw, float* scratch, int n_img,
+                                       int channels, int hw, int* deferred_slabs, const sgmcmc_reduce_job* jobs,
+                                       int n_jobs, int riders_first, void* stream) {
+  SGMCMC_FRESH_ERROR_STATE();
+  if (n_jobs < 0 || n_jobs > SGMCMC_RIDE_JOBS || (n_jobs && !jobs)) return (int)hipErrorInvalidValue;
+  conv::RideJobs R{};
+  R.n = n_jobs;
+  R.first = riders_first != 0;
+  int blocks = 0;
+  for (int j = 0; j < n_jobs; ++j) {
+    const sgmcmc_reduce_job& q = jobs[j];
+    if (!q.part || !q.out || q.n_slabs <= 0 || q.numel <= 0 || (q.taps > 1 && q.numel % q.taps)) return (int)hipErrorInvalidValue;
+    R.job[j] = q;
+    R.first_block[j] = blocks;
+    blocks += conv::reduce_blocks(q.n_slabs, q.numel);
+  }
+  R.first_block[n_jobs] = blocks;
+  return conv3x3_bwd_ex_with(x, w, dy, dx, epi, dw, scratch, n_img, channels, hw, deferred_slabs, stream, R);
 }
 
 #ifdef SGMCMC_STAMPS

@@ -251,8 +251,8 @@ def _conv_bwd_ex(lib, x, w, dy, s, add=None, sums_for=None, G=1):
         # the weight-gradient slabs leave the critical path: side stream, joined before the pass's slab reduction
         _conv.split_backward(lib, x, w, dy, dx, E, part, slabs)
     else:
-        err = lib.sgmcmc_conv3x3_bwd_ex(x.data_ptr(), w.data_ptr(), dy.data_ptr(), dx.data_ptr(), ctypes.byref(E), 0,
-                                        part.data_ptr(), n, c, hw, ctypes.byref(slabs), s)
+        # (slab reductions pending from earlier launches of this pass ride in this one: conv.take_riders)
+        err = _conv.bwd_ex(lib, x, w, dy, dx, E, None, part, slabs, s, _conv.take_riders(c, hw))
         if err:
             _hip.check(err, "sgmcmc_conv3x3_bwd_ex")
     return dx, _reduce_or_defer(lib, w, part, slabs.value, s), partial, n_partials

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGMCMC_ABI_VERSION 10
+#define SGMCMC_ABI_VERSION 11
 #define SGMCMC_CHUNK 4096 /* default elements per arena chunk = 256 threads x 4 items x 4 elements */
 #define SGMCMC_CHUNK_SMALL 1024 /* small models: one item per thread, 4x more workgroups */
 #define SGMCMC_NSUMS 6
@@ -498,6 +498,17 @@ int sgmcmc_conv3x3_bwd_ex(const float* x, const float* w, const float* dy, float
                           const sgmcmc_conv_bwd_epilogue* epi, float* dw, float* scratch, int n_img, int channels,
                           int hw, int* deferred_slabs, void* stream);
 int sgmcmc_wrw_reduce_many(const sgmcmc_reduce_job* jobs, int n_jobs, void* stream);
+/* sgmcmc_conv3x3_bwd_ex whose launch ALSO reduces the slabs of up to SGMCMC_RIDE_JOBS earlier launches (`jobs`, as for
+ * sgmcmc_wrw_reduce_many: the same blocks, the same bits) in a few extra workgroups -- riders.  Every job's slabs must
+ * have been written by work enqueued EARLIER on `stream`: the kernel boundary is the only synchronisation.  The
+ * reductions leave the dependent chain of a backward pass: a rider waits for memory in a workgroup slot that the
+ * launch's own roles have no use for.  n_jobs = 0 is sgmcmc_conv3x3_bwd_ex.  riders_first != 0: the riders lead the grid
+ * (padded to 8 blocks) instead of trailing it; the other workgroups run where they run without riders either way. */
+#define SGMCMC_RIDE_JOBS 4
+int sgmcmc_conv3x3_bwd_ride(const float* x, const float* w, const float* dy, float* dx,
+                            const sgmcmc_conv_bwd_epilogue* epi, float* dw, float* scratch, int n_img, int channels,
+                            int hw, int* deferred_slabs, const sgmcmc_reduce_job* jobs, int n_jobs, int riders_first,
+                            void* stream);
 
 #define SGMCMC_FRAG_JOBS 24   /* convolutions per launch of sgmcmc_conv3x3_prepare_weights */
 /* ---- the same three contractions, PERSISTENT kernels on prepared weight fragments (csrc/conv2_hip.inc; round 3) ----
