@@ -24,7 +24,7 @@ INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 SOURCES = [os.path.join(_HERE, "csrc", "sgmcmc_hip.hip")]
 SOURCE = SOURCES[0]
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 CHUNK = 4096
 CHUNK_SMALL = 1024
 NSUMS = 6
@@ -229,6 +229,9 @@ EXPORTS = {
     "sgmcmc_dense_step_multi": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(DenseChain), ctypes.c_int,
                                                ctypes.POINTER(StepArgs), ctypes.c_void_p, ctypes.POINTER(StepArgs),
                                                ctypes.c_void_p]),
+    "sgmcmc_dense_step_multi_args": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(DenseChain), ctypes.c_int,
+                                                    ctypes.POINTER(StepArgs), ctypes.c_void_p, ctypes.POINTER(StepArgs),
+                                                    ctypes.c_void_p]),
     "sgmcmc_finalize": (ctypes.c_int, [ctypes.POINTER(Layout), ctypes.POINTER(StepArgs),
                                        ctypes.c_void_p]),
     "sgmcmc_accumulate_parts": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,

@@ -765,8 +765,9 @@ __global__ __launch_bounds__(kSplitThreads) void mlp_rest_kernel(sgmcmc_mlp_args
 // ---- several independent chains per launch (blockIdx.y = chain): the small nets use 33-46 workgroups of a
 // 256-CU GPU per launch; K chains of the same architecture stepped in lock-step share the three launches of a
 // leapfrog step.  Per-chain pointers (weights, partial-gradient scratch, sampler arena) come from a device-resident
-// table written once; what changes per step -- the transition's scalars (the same for every chain: same schedule)
-// and each chain's 128 row indices -- travels BY VALUE in the kernel arguments (16-bit indices: 8 chains x 256 B).
+// table written once; what changes per step -- the transition's scalars (one block when every chain has the same
+// schedule, else one block per chain: the *_args kernels below) and each chain's 128 row indices -- travels BY VALUE
+// in the kernel arguments (16-bit indices: 8 chains x 256 B).
 struct IdxMulti { uint16_t idx[SGMCMC_MAX_CHAINS][SGMCMC_MLP_BATCH_MULTI]; };
 
 __global__ __launch_bounds__(kSplitThreads) void mlp_f1_multi_kernel(const sgmcmc_dense_chain* __restrict__ T,
@@ -798,7 +799,37 @@ __global__ __launch_bounds__(kThreads) void step_parts_multi_kernel(const sgmcmc
   const Early<float, 1> E = step_early<float, true, 1>(L, A.chunk_begin);
   step_body<float, KIND, true, 1, true, false, false, true>(L, A, G, &E);
 }
+
+// ---- the same launches with EACH chain's own transition scalars (a temperature ladder, a step-size sweep): chain c
+// reads block c of an array passed by value (8 x 128 B = 1 KiB of kernel arguments; the 2 KiB of row indices go to the
+// other launch).  blockIdx.y is a workgroup id, so the block is wave-uniform and lands in SGPRs as the single block
+// does; every decision of the transition body (draw / no draw, momentum decay, clamp) is taken from it.
+struct ArgsMulti { sgmcmc_step_args a[SGMCMC_MAX_CHAINS]; };
+
+template <int KIND>
+__global__ __launch_bounds__(kThreads) void step_parts_multi_args_kernel(const sgmcmc_dense_chain* __restrict__ T,
+                                                                         ArgsMulti AM) {
+  const int c = blockIdx.y;
+  const sgmcmc_layout L = T[c].layout;
+  const sgmcmc_mlp_args& M = T[c].mlp;
+  const int slices = (M.batch + ROWS - 1) / ROWS;
+  const GradParts G = {M.gpart, slices, M.gpart_stride, M.loss_part, M.correct_part, M.batch, T[c].num_data};
+  sgmcmc_step_args A = AM.a[c];
+  A.stream = T[c].chain_id;
+  const Early<float, 1> E = step_early<float, true, 1>(L, A.chunk_begin);
+  step_body<float, KIND, true, 1, true, false, false, true>(L, A, G, &E);
+}
 }  // extern "C++"
+
+__global__ __launch_bounds__(kSplitThreads) void mlp_rest_multi_args_kernel(const sgmcmc_dense_chain* __restrict__ T,
+                                                                            ArgsMulti AM, int with_finalize) {
+  const int c = blockIdx.y;
+  const sgmcmc_mlp_args P = T[c].mlp;
+  const sgmcmc_layout L = T[c].layout;
+  sgmcmc_step_args Aprev = AM.a[c];
+  Aprev.stream = T[c].chain_id;
+  mlp_rest_body(P, L, Aprev, with_finalize);
+}
 }  // namespace
 
 int64_t sgmcmc_mlp_split_scratch_floats(int batch) {
@@ -886,6 +917,59 @@ int sgmcmc_dense_step_multi(const sgmcmc_dense_chain* chains_dev, const sgmcmc_d
     case SGMCMC_HMC: SGMCMC_LAUNCH(step_parts_multi_kernel<SGMCMC_HMC>, grid, block, 0, s, chains_dev, *A); break;
     case SGMCMC_SGLD: SGMCMC_LAUNCH(step_parts_multi_kernel<SGMCMC_SGLD>, grid, block, 0, s, chains_dev, *A); break;
     default: return (int)hipErrorInvalidValue;
+  }
+  return (int)hipGetLastError();
+}
+
+int sgmcmc_dense_step_multi_args(const sgmcmc_dense_chain* chains_dev, const sgmcmc_dense_chain* chain0_host,
+                                 int n_chains, const sgmcmc_step_args* A, const uint16_t* idx_host,
+                                 const sgmcmc_step_args* A_pending, void* stream) {
+  // host-side validation first: nothing below touches the runtime before the blocks are known to agree
+  if (!chains_dev || !chain0_host || !A || !idx_host || n_chains <= 0 || n_chains > SGMCMC_MAX_CHAINS)
+    return (int)hipErrorInvalidValue;
+  const sgmcmc_mlp_args& mlp = chain0_host->mlp;
+  const sgmcmc_layout& L = chain0_host->layout;
+  if (mlp.batch <= 0 || mlp.batch > SGMCMC_MLP_BATCH_MULTI || (mlp.in_features & 3) || mlp.hidden1 > HP ||
+      mlp.hidden2 > HP || mlp.out_features > OP || !mlp.split_scratch || L.dtype != SGMCMC_F32 ||
+      L.chunk_elems != SGMCMC_CHUNK_SMALL || (A->flags & SGMCMC_UNALIGNED) || !(A->flags & SGMCMC_SMALL_FINALIZE) ||
+      !(A->flags & SGMCMC_DEFER_FINALIZE))
+    return (int)hipErrorInvalidValue;
+  if (A->kind != SGMCMC_VERLET && A->kind != SGMCMC_HMC && A->kind != SGMCMC_SGLD) return (int)hipErrorInvalidValue;
+  if (A->chunk_end <= A->chunk_begin) return (int)hipErrorInvalidValue;
+  // the template parameter, the launch geometry, the sweep counter and the metric cadence are one per launch
+  for (const sgmcmc_step_args* B : {A, A_pending}) {
+    if (!B) continue;
+    for (int c = 1; c < n_chains; ++c)
+      if (B[c].kind != B[0].kind || B[c].flags != B[0].flags || B[c].seg_begin != B[0].seg_begin ||
+          B[c].seg_end != B[0].seg_end || B[c].chunk_begin != B[0].chunk_begin || B[c].chunk_end != B[0].chunk_end ||
+          B[c].draw != B[0].draw)
+        return (int)hipErrorInvalidValue;
+  }
+  if (A_pending && !(A_pending->flags & SGMCMC_SMALL_FINALIZE)) return (int)hipErrorInvalidValue;
+  const int steps16 = ((mlp.in_features + 15) & ~15) >> 4;
+  if ((steps16 + KSPLIT - 1) / KSPLIT > F1_UNROLL) return (int)hipErrorInvalidValue;
+  SGMCMC_FRESH_ERROR_STATE();
+  IdxMulti IM;
+  for (int c = 0; c < n_chains; ++c)
+    for (int b = 0; b < mlp.batch; ++b) IM.idx[c][b] = idx_host[(size_t)c * mlp.batch + b];
+  ArgsMulti AM, AP;
+  for (int c = 0; c < SGMCMC_MAX_CHAINS; ++c) {      // (unused rows repeat chain 0: no uninitialised kernel argument)
+    const int k = c < n_chains ? c : 0;
+    AM.a[c] = A[k];
+    AP.a[c] = A_pending ? A_pending[k] : A[k];
+    AP.a[c].flags &= ~(uint32_t)SGMCMC_DEFER_FINALIZE;
+  }
+  const int slices = (mlp.batch + ROWS - 1) / ROWS;
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned ny = (unsigned)n_chains;
+  SGMCMC_LAUNCH(mlp_f1_multi_kernel, dim3((unsigned)(slices * KSPLIT), ny), dim3(kSplitThreads), 0, s, chains_dev, IM);
+  SGMCMC_LAUNCH(mlp_rest_multi_args_kernel, dim3((unsigned)(slices * KSPLIT + (A_pending ? 1 : 0)), ny),
+                dim3(kSplitThreads), 0, s, chains_dev, AP, A_pending ? 1 : 0);
+  const dim3 grid((unsigned)(A->chunk_end - A->chunk_begin), ny), block(kThreads);
+  switch (A->kind) {
+    case SGMCMC_VERLET: SGMCMC_LAUNCH(step_parts_multi_args_kernel<SGMCMC_VERLET>, grid, block, 0, s, chains_dev, AM); break;
+    case SGMCMC_HMC: SGMCMC_LAUNCH(step_parts_multi_args_kernel<SGMCMC_HMC>, grid, block, 0, s, chains_dev, AM); break;
+    default: SGMCMC_LAUNCH(step_parts_multi_args_kernel<SGMCMC_SGLD>, grid, block, 0, s, chains_dev, AM); break;
   }
   return (int)hipGetLastError();
 }

@@ -281,9 +281,16 @@ class FusedDenseLeapfrog(_ReportSlots):
             r = dict(loss=float(v[4]), acc=float(v[5]), nonfinite=bool(v[1] != 0.0),
                      log_prior=float(v[2]), energy=float(v[3]))
             return r, v[8:].reshape(n_seg, -1).copy()
-        row = PendingRow(self, buf, ev, parse)
+        return self._hand_over(PendingRow(self, buf, ev, parse), wait)
+
+    def _hand_over(self, row, wait):
+        """what ``replay`` returns on a metric step, given the row's read-back (``get()`` -> (dict, per-segment state)):
+        the row itself when the caller does not wait, else its dict -- with the state left for the per-tensor reads and
+        the non-finite flag re-armed.  (``multichain.run_dense_lockstep`` hands a chain ITS row of a joint step over
+        through this too.)"""
         if not wait:
             return row
+        eng = self.eng
         r, state = row.get()
         eng._state_host = state
         if r["nonfinite"]:
@@ -293,15 +300,22 @@ class FusedDenseLeapfrog(_ReportSlots):
 
 class MultiChainDense:
     """K independent chains of the dense classifier stepped in lock-step by THREE launches per leapfrog step
-    (``sgmcmc_dense_step_multi``: grid dimension y = chain) instead of 3 K.
+    (``sgmcmc_dense_step_multi`` / ``sgmcmc_dense_step_multi_args``: grid dimension y = chain) instead of 3 K.
 
     One chain's launches occupy 33-46 workgroups of the 256 CUs and are latency-bound (a step is three dependent
     launches of 6-12 us whatever the net's size); chains are independent, so K of them -- each with its own
     ``FusedDenseLeapfrog`` (weights, sampler arena, data order, Philox stream) -- share the launches and the GPU does
-    K steps in about the time of one.  All chains must have one architecture and one schedule (learning rate,
-    temperature, metrics cadence): the transition's scalars travel once, by value.  Chain c's trajectory is
-    bit-identical to the same chain stepped alone (tests/test_fused_dense.py).  This is an addition to the
-    reference's one-process-per-chain model (experiments/run_experiment.sh:15-34), for the small nets only."""
+    K steps in about the time of one.  All chains must have one architecture, one sampler kind, one batch size and one
+    metrics cadence, and they share the sweep counter (``engine.draw``): those are properties of the launch.  Everything
+    that is a scalar of the transition may differ from chain to chain -- learning rate, temperature (0 included: that
+    chain draws no noise), momentum, ``num_data``, ``rmsprop_alpha``, the gradient clamp, the Philox seed -- and so may
+    the prior family of every tensor (it comes from the chain's own segment table): a temperature ladder or a sweep
+    over step sizes is one ``MultiChainDense``.  Chains whose scalars all agree take ``sgmcmc_dense_step_multi`` (one
+    128-byte block for all of them, as before); otherwise every chain's own block travels by value
+    (``sgmcmc_dense_step_multi_args``, K x 128 bytes).  Either way chain c's trajectory is bit-identical to the same
+    chain stepped alone (tests/test_fused_dense.py, tests/test_dense_ladder.py).  This is an addition to the
+    reference's one-process-per-chain model (experiments/run_experiment.sh:15-34), for the small nets only;
+    ``multichain.run_dense_lockstep`` drives whole runners through it."""
 
     def __init__(self, steppers):
         self.steppers = list(steppers)
@@ -314,6 +328,8 @@ class MultiChainDense:
                 raise ValueError("multi-chain stepping needs the direct, split fused dense path")
             if [tuple(p.shape) for p in s.eng.params] != [tuple(p.shape) for p in s0.eng.params]:
                 raise ValueError("chains must share one architecture")
+            if s.opt._KIND != s0.opt._KIND:
+                raise ValueError("chains must share one sampler kind (it selects the kernel)")
             if s.X.shape[0] > 65536:
                 raise ValueError("16-bit row indices: data sets of up to 65,536 rows")
             if s.eng.prior_flags() != 0:
@@ -324,6 +340,12 @@ class MultiChainDense:
         self._uploaded = None
         self._sig = None
         self._idx16 = np.zeros((K, _hip.MLP_BATCH_MULTI), dtype=np.uint16)
+        # per-chain argument blocks (ping-pong: the previous step's are still pending) and the pending ones, gathered
+        self._blocks = [(_hip.StepArgs * K)(), (_hip.StepArgs * K)()]
+        self._refs = [[arr[c] for c in range(K)] for arr in self._blocks]
+        self._pend = (_hip.StepArgs * K)()
+        self._bp = 0
+        self._seeded = [None, None]                # the table signature each array's static fields were filled under
 
     def _table(self, batch):
         "per-chain pointers, uploaded when any of them changed (first use, roll-back arrays allocated, ...)"
@@ -352,52 +374,119 @@ class MultiChainDense:
             self._dev.copy_(torch.frombuffer(bytearray(raw), dtype=torch.uint8))     # synchronous: rare
             self._uploaded = raw
 
-    def step(self, idx_list, metrics=False):
-        """one leapfrog step of every chain on ITS rows ``idx_list[c]`` (host int arrays of one length <= 128).
-        ``metrics``: the transition also updates the temperature estimates / log-prior; returns one
-        dict(loss, acc, log_prior, energy, nonfinite) per chain (after one read-back each), else None."""
-        K, batch = len(self.steppers), len(idx_list[0])
-        if batch > _hip.MLP_BATCH_MULTI or any(len(i) != batch for i in idx_list):
+    _SAME = ctypes.sizeof(_hip.StepArgs) - 8       # a block up to its `stream` (the chain id: every chain's own)
+
+    def step(self, idx_list, metrics=False, calc_metrics=None):
+        """one leapfrog step of every chain on ITS rows ``idx_list[c]`` (host int arrays of one length <= 128), each
+        chain with the scalars of ITS optimizer as they are now (lr, temperature, momentum, ...).
+        ``metrics``: returns one dict(loss, acc, log_prior, energy, nonfinite) per chain (after one read-back for
+        all), else None; the transition also updates the temperature estimates / log-prior unless
+        ``calc_metrics=False`` (the loss and accuracy of this forward pass alone: what
+        ``FusedDenseLeapfrog.replay(..., metrics=True, calc_metrics=False)`` gives one chain).
+        ValueError, before any chain is stepped or its sweep counter advanced: chains whose sweep counters differ, that
+        do not agree on having a momentum (SGLD) or on the static flags of the transition."""
+        steppers = self.steppers
+        K, batch = len(steppers), len(idx_list[0])
+        if len(idx_list) != K or batch > _hip.MLP_BATCH_MULTI or any(len(i) != batch for i in idx_list):
             raise ValueError("one batch size of at most 128 rows for all chains")
+        cm = metrics if calc_metrics is None else calc_metrics
+        s0 = steppers[0]
+        g0 = s0.opt.param_groups[0]
+        d0, lr0, t0, a0, n0, r0 = s0.eng.draw, g0["lr"], g0["temperature"], g0["momentum"], g0["num_data"], g0["rmsprop_alpha"]
+        uniform = True
+        for s in steppers[1:]:
+            if s.eng.draw != d0:
+                raise ValueError("chains stepped together must share the draw counter (engine.draw): "
+                                 f"{[x.eng.draw for x in steppers]}")
+            g = s.opt.param_groups[0]
+            if (g["lr"] != lr0 or g["temperature"] != t0 or g["momentum"] != a0 or g["num_data"] != n0
+                    or g["rmsprop_alpha"] != r0 or s.opt.grad_clamp != s0.opt.grad_clamp or s.eng.seed != s0.eng.seed):
+                uniform = False
+                if (g["momentum"] > 0) != (a0 > 0):
+                    raise ValueError("chains stepped together must agree on having a momentum (a flag of the launch)")
         self._table(batch)
-        s0 = self.steppers[0]
-        st0 = s0._by_batch[batch]
-        s0._pp ^= 1
-        A = s0._args(st0["App"][s0._pp], metrics)
-        A.flags |= _hip.DEFER_FINALIZE
-        for s in self.steppers[1:]:
-            d = s.eng.next_draw()
-            if d != A.draw or s.opt.param_groups[0]["lr"] != s0.opt.param_groups[0]["lr"]:
-                raise RuntimeError("chains stepped together must share the schedule and the draw counter")
         for c, idx in enumerate(idx_list):
             self._idx16[c, :batch] = idx
-        # the launch finalizes ONE deferred transition for all chains: they must agree on what is pending.  A chain
-        # flushed on its own (a state read, a preconditioner refresh) while another was not would otherwise have its
-        # bookkeeping run twice -- or the others' dropped: settle every chain first.
-        pend = [s.eng.pending for s in self.steppers]
-        p0 = pend[0]
-        if any((p is None) != (p0 is None) or (p is not None and (p.draw != p0.draw or p.flags != p0.flags))
-               for p in pend[1:]):
-            for s in self.steppers:
-                s.eng.flush()
-        pending = s0.eng.pending
         idx16 = np.ascontiguousarray(self._idx16[:, :batch])
-        err = self.lib.sgmcmc_dense_step_multi(self._dev.data_ptr(), ctypes.byref(self._host[0]), K, A,
-                                               idx16.ctypes.data, pending, s0.eng.stream())
-        if err:
-            _hip.check(err, "sgmcmc_dense_step_multi")
-        for s in self.steppers:
-            s.eng.pending = A
+        pend = [s.eng.pending for s in steppers]
+        p0 = pend[0]
+        if uniform:
+            # every chain's block would be the same bytes up to its chain id: ONE block for all (the call, and the
+            # bits, of before there were per-chain blocks)
+            st0 = s0._by_batch[batch]
+            s0._pp ^= 1
+            A = s0._args(st0["App"][s0._pp], cm)
+            A.flags |= _hip.DEFER_FINALIZE
+            for s in steppers[1:]:
+                s.eng.next_draw()
+            # the launch finalizes ONE deferred transition for all chains: they must agree on what is pending.  A chain
+            # flushed on its own (a state read, a preconditioner refresh) while another was not would otherwise have its
+            # bookkeeping run twice -- or the others' dropped: settle every chain first.  (Likewise chains whose last
+            # step had blocks of their own.)
+            if any(p is not p0 and ((p is None) != (p0 is None) or p0 is None
+                                    or bytes(p)[:self._SAME] != bytes(p0)[:self._SAME]) for p in pend[1:]):
+                for s in steppers:
+                    s.eng.flush()
+            pending = s0.eng.pending
+            err = self.lib.sgmcmc_dense_step_multi(self._dev.data_ptr(), ctypes.byref(self._host[0]), K, A,
+                                                   idx16.ctypes.data, pending, s0.eng.stream())
+            if err:
+                _hip.check(err, "sgmcmc_dense_step_multi")
+            for s in steppers:
+                s.eng.pending = A
+        else:
+            f0 = s0._static_flags
+            if any(s._static_flags != f0 for s in steppers[1:]):
+                raise ValueError("chains stepped together must share the transition's flags: "
+                                 f"{[s._static_flags for s in steppers]}")
+            bp = self._bp ^ 1
+            blocks, refs = self._blocks[bp], self._refs[bp]
+            # the array about to be written is never one a chain's deferred transition still reads: normally the pending
+            # blocks are the OTHER array's (or a stepper's own); whatever led here otherwise, settle first
+            mine = {ctypes.addressof(A) for A in refs}
+            if any(p is not None and ctypes.addressof(p) in mine for p in pend):
+                for s in steppers:
+                    s.eng.flush()
+                pend = [None] * K
+                p0 = None
+            if self._seeded[bp] is not self._sig:  # what _args leaves alone: kind, ranges, clamp, seed, chain id
+                for s, A in zip(steppers, refs):
+                    ctypes.memmove(ctypes.addressof(A), ctypes.addressof(s._by_batch[batch]["App"][0]),
+                                   ctypes.sizeof(_hip.StepArgs))
+                self._seeded[bp] = self._sig
+            self._bp = bp
+            for s, A in zip(steppers, refs):
+                s._args(A, cm)
+                A.flags |= _hip.DEFER_FINALIZE
+            # one deferred transition PER CHAIN is finalized by the launch, each with its own block; the chains must
+            # still agree on whether one is pending, and on its flags and sweep index: else settle every chain first
+            if any((p is None) != (p0 is None) or (p is not None and (p.draw != p0.draw or p.flags != p0.flags))
+                   for p in pend[1:]):
+                for s in steppers:
+                    s.eng.flush()
+                p0 = None
+            pending = None
+            if p0 is not None:
+                pending = self._pend
+                for c, p in enumerate(pend):
+                    ctypes.memmove(ctypes.addressof(pending[c]), ctypes.addressof(p), ctypes.sizeof(_hip.StepArgs))
+            err = self.lib.sgmcmc_dense_step_multi_args(self._dev.data_ptr(), ctypes.byref(self._host[0]), K, blocks,
+                                                        idx16.ctypes.data, pending, s0.eng.stream())
+            if err:
+                _hip.check(err, "sgmcmc_dense_step_multi_args")
+            for s, A in zip(steppers, refs):
+                s.eng.pending = A
+        for s in steppers:
             s.eng._state_host = None
             s.eng.energy_ready = True
         if not metrics:
             return None
-        for s in self.steppers:
+        for s in steppers:
             s.eng.flush()                    # every chain's bookkeeping, now (the rows read its results) ...
             s.eng.metrics_ready = True
-        rows = torch.stack([s.eng.report for s in self.steppers]).cpu().numpy()      # ... and ONE read-back for all
+        rows = torch.stack([s.eng.report for s in steppers]).cpu().numpy()      # ... and ONE read-back for all
         out = []
-        for s, v in zip(self.steppers, rows):
+        for s, v in zip(steppers, rows):
             out.append(dict(loss=float(v[4]), acc=float(v[5]), nonfinite=bool(v[1] != 0.0), log_prior=float(v[2]),
                             energy=float(v[3])))
             s.eng._state_host = v[8:].reshape(s.eng.n_seg, -1).copy()

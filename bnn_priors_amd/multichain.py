@@ -4,11 +4,13 @@ A captured step of the convolutional nets is a chain of ~90 dependent launches, 
 its boundaries; independent chains fill those gaps (googleresnet: 1.36x one chain's throughput with two chains on two
 streams, profiles/r02_bench_googleresnet_stream_chains.json).  The reference runs one chain per process
 (experiments/run_experiment.sh:15-34); this is the same set of independent Markov chains -- own model, own data order,
-Philox stream = ``chain_id`` -- scheduled differently.  For the dense classifier use ``fused_dense.MultiChainDense``
-(chains as a grid dimension of the step's kernels) instead.
+Philox stream = ``chain_id`` -- scheduled differently.  For the dense classifier use ``run_dense_lockstep`` instead:
+the chains are a grid dimension of the step's kernels (``fused_dense.MultiChainDense``), and they may differ in
+temperature, learning rate, momentum and prior -- a cold-posterior ladder in one process.
 
     runners = [runner_class("VerletSGLDReject")(model=make_model(), ..., seed=1234, chain_id=c) for c in range(2)]
     multichain.run_on_streams(runners)         # == r.run() for every r, interleaved step by step
+    multichain.run_dense_lockstep(runners)     # == r.run() for every r, every leapfrog step ONE set of launches
 """
 import time
 
@@ -168,3 +170,200 @@ def run_on_streams(runners, streams=None):
                     alive.remove(k)
     for s in streams:
         main.wait_stream(s)
+
+
+# ------------------------------------------------------------------ dense classifier: K runners, one set of launches per step
+class _ReadyRow:
+    "a metric row whose read-back has happened (what ``FusedDenseLeapfrog.replay(..., wait=False)`` hands a runner)"
+
+    def __init__(self, r, state):
+        self._r, self._state = r, state
+
+    def ready(self):
+        return True
+
+    def get(self):
+        return self._r, self._state
+
+
+class _LockstepPort:
+    """Stands where a runner's ``FusedDenseLeapfrog`` stands while ``run_dense_lockstep`` drives it: ``replay`` hands the
+    minibatch to the group and returns once ALL chains' steps have been launched together; everything else (``exact``,
+    ``X_source``, ...) is the chain's own stepper."""
+
+    def __init__(self, group, c, stepper):
+        self._group, self._c, self._stepper = group, c, stepper
+
+    def __getattr__(self, name):
+        return getattr(self._stepper, name)
+
+    def replay(self, idx, metrics=False, idx_ptr=None, wait=True, calc_metrics=None):
+        return self._group.submit(self._c, idx, metrics, wait, calc_metrics)
+
+
+class _Lockstep:
+    """The K generators of ``run_dense_lockstep``.  A chain that reaches a leapfrog step waits inside ``submit`` while the
+    chains that have not reached theirs are advanced (each in turn waits likewise); the last one to arrive launches the
+    step for all, and every chain then goes on from where it was -- with its own scheduler step, M-H point, roll-back,
+    evaluation.  A chain's own scalars are read when the launch is made, i.e. before any chain's code after its step
+    has run: exactly the values it would have stepped with alone."""
+
+    def __init__(self, runners):
+        self.runners = runners
+        self.K = len(runners)
+        self.ports = [None] * self.K
+        self.req = [None] * self.K
+        self.out = None
+        self.multi = None
+        self.gens = None
+        self.done = [False] * self.K
+
+    def port(self, c):
+        "runner c's ``_fused_dense()`` while it is driven: the port in front of ITS stepper (never None: no fallback)"
+        if self.ports[c] is None:
+            r = self.runners[c]
+            real = type(r)._fused_dense(r)
+            if real is None:
+                raise ValueError(f"run_dense_lockstep: runner {c} has no fused dense step (_fused_dense() is None): its "
+                                 "model, priors or data set are not what fused_dense.FusedDenseLeapfrog supports")
+            self.ports[c] = _LockstepPort(self, c, real)
+        return self.ports[c]
+
+    def advance(self, c):
+        try:
+            next(self.gens[c])
+        except StopIteration:
+            self.done[c] = True
+
+    def submit(self, c, idx, metrics, wait, calc_metrics):
+        assert self.req[c] is None
+        self.req[c] = (idx, bool(metrics), calc_metrics)
+        mine = self.round
+        if all(q is not None for q in self.req):
+            self._launch()
+        while self.round == mine:        # the others have not all arrived: bring them to their step
+            j = next((j for j in range(self.K) if self.req[j] is None), None)
+            if j is None or self.done[j]:
+                raise RuntimeError(f"run_dense_lockstep: chain {c} is at a leapfrog step that chain {j} never reaches "
+                                   "(the runners are not in lock-step)")
+            self.advance(j)
+        if not metrics:
+            return None
+        stepper = self.ports[c]._stepper
+        state, stepper.eng._state_host = stepper.eng._state_host, None
+        return stepper._hand_over(_ReadyRow(self.out[c], state), wait)
+
+    round = 0
+
+    def _launch(self):
+        from .fused_dense import MultiChainDense
+        if self.multi is None:
+            self.multi = MultiChainDense([p._stepper for p in self.ports])
+        idx, metrics, calc = self.req[0]
+        if any(q[1] != metrics or q[2] != calc or len(q[0]) != len(idx) for q in self.req[1:]):
+            raise RuntimeError("run_dense_lockstep: the chains disagree on this step's metrics or batch size "
+                               "(the runners are not in lock-step)")
+        out = self.multi.step([q[0] for q in self.req], metrics=metrics, calc_metrics=calc)
+        self.out = out
+        self.req = [None] * self.K
+        self.round += 1
+
+
+def _lockstep_check(runners):
+    "everything that can be told before a runner has an optimizer: ValueError when the runners cannot be stepped together"
+    from . import _hip
+    from .fused_dense import _dense_layers
+    from .prior import named_priors
+    if not 1 <= len(runners) <= _hip.MAX_CHAINS:
+        raise ValueError(f"run_dense_lockstep: 1..{_hip.MAX_CHAINS} (SGMCMC_MAX_CHAINS) runners, got {len(runners)}")
+    r0 = runners[0]
+
+    def shapes(r):
+        return [tuple(p.shape) for p in r._params]
+
+    def layout(r):
+        dl = r.dataloader
+        return dict(rows=len(dl.dataset), batch_size=dl.batch_size, batches=len(dl), drop_last=dl.drop_last,
+                    metrics_skip=r.metrics_skip, epochs_per_cycle=r.epochs_per_cycle, warmup_epochs=r.warmup_epochs,
+                    sample_epochs=r.sample_epochs, skip=r.skip, cycles=r.cycles, precond_update=r.precond_update,
+                    reject_samples=r.reject_samples, trajectory_length=getattr(r, "trajectory_length", None),
+                    has_momentum=r.momentum > 0, device=r._device)
+    for c, r in enumerate(runners):
+        if type(r) is not type(r0):
+            raise ValueError(f"run_dense_lockstep: runner {c} is a {type(r).__name__}, runner 0 a {type(r0).__name__}")
+        if shapes(r) != shapes(r0):
+            raise ValueError(f"run_dense_lockstep: runner {c}'s architecture {shapes(r)} is not runner 0's {shapes(r0)}")
+        a, b = layout(r), layout(r0)
+        if a != b:
+            diff = {k: (a[k], b[k]) for k in a if a[k] != b[k]}
+            raise ValueError(f"run_dense_lockstep: runner {c} and runner 0 differ in {diff}: chains in lock-step share the "
+                             "data set size, batch size, metrics cadence and the cycle / epoch layout")
+        if not r.use_graph or _dense_layers(r.model) is None:
+            raise ValueError(f"run_dense_lockstep: runner {c}'s model is not the dense classifier of the fused step "
+                             "(or use_graph=False)")
+        if [len(sh) for sh in shapes(r)] != [2, 1, 2, 1, 2, 1]:
+            raise ValueError(f"run_dense_lockstep: runner {c}'s parameters {shapes(r)} are not three Linear layers'")
+        (h1, i), _, (h2, _), _, (o, _), _ = shapes(r)
+        if (i % 4 or h1 > 64 or h2 > 64 or o > 16 or any(p.dtype != torch.float32 for p in r._params)
+                or _hip.lib().sgmcmc_mlp_lds_bytes(i) > 160 * 1024):
+            raise ValueError(f"run_dense_lockstep: runner {c}'s layer sizes {shapes(r)} / dtype are not the fused dense "
+                             "step's (float32, inputs a multiple of 4, hidden <= 64, classes <= 16)")
+        if not getattr(r._batches(), "fast", False):
+            raise ValueError(f"run_dense_lockstep: runner {c}'s data set is not device resident (a TensorDataset of two "
+                             "tensors behind a plain DataLoader): the fused dense step gathers its rows by index")
+        for name, pr in named_priors(r.model):
+            if getattr(pr, "is_component", False):
+                continue
+            spec = pr.fused_spec()
+            if spec is None or spec[0] > _hip.PRIOR_CAUCHY or pr.scale_link() is not None:
+                raise ValueError(f"run_dense_lockstep: runner {c}'s prior {name} ({type(pr).__name__}) is not one the "
+                                 "multi-chain kernels carry (constant-scale Normal, Laplace, Student-t, Cauchy)")
+    dl = r0.dataloader
+    if dl.batch_size is None or dl.batch_size > _hip.MLP_BATCH_MULTI or len(dl.dataset) > 65536:
+        raise ValueError(f"run_dense_lockstep: batches of at most {_hip.MLP_BATCH_MULTI} rows of a data set of at most "
+                         "65,536 rows")
+    if r0.reject_samples:
+        zero = [r.temperature == 0 for r in runners]
+        if any(zero) and not all(zero):
+            # maybe_reject draws its uniform only when T > 0: such chains would leave the shared sweep counter
+            raise ValueError("run_dense_lockstep: with reject_samples, chains at temperature 0 and chains above it do not "
+                             "consume the same Philox sweep indices and cannot share a launch")
+
+
+def run_dense_lockstep(runners):
+    """``runner.run()`` for every one of K runners of the dense classifier, every ordinary minibatch leapfrog step of the
+    K chains being ONE ``MultiChainDense.step`` (three launches for all of them).  The runners are of one class (any
+    of the six), one architecture, one data-set size and batch size and one ``metrics_skip`` / cycle / epoch layout;
+    they may differ in temperature, learning rate, momentum, priors, seeds, ``cycle_seed`` and sinks -- the ladder
+    of a cold-posterior sweep.  Everything but the leapfrog step is each chain's own runner code, in the order it runs
+    it alone: ``begin()``, M-H points with their exact pass, roll-backs (a chain that rejects rolls back alone),
+    evaluation, stored samples, scheduler steps, preconditioner updates, metric rows.  Every chain's metrics and samples
+    are those of ``runner.run()`` alone, bit for bit (tests/test_dense_ladder.py).
+
+    ValueError before anything runs when the runners cannot be stepped together -- class, shapes, layout, priors,
+    data source, layer sizes: every reason for a missing fused dense step that can be told from the runner and its model.
+    What only the runner's optimizer can tell (it exists once ``run_iter`` has made it: several parameter groups, an
+    arena too large for the one-workgroup finalize) is caught where the runner first asks for its stepper, as a
+    ValueError too: before any leapfrog step of any chain, but after the ``begin()`` -- exact pass, first
+    ``initial_step``, metric row 0 -- of the runners before it.  There is no fallback to stepping a chain on its own."""
+    runners = list(runners)
+    if not runners:
+        return
+    _lockstep_check(runners)
+    group = _Lockstep(runners)
+    for c, r in enumerate(runners):
+        if "_fused_dense" in r.__dict__:
+            raise ValueError(f"run_dense_lockstep: runner {c} is being driven already")
+    try:
+        for c, r in enumerate(runners):
+            r._fused_dense = (lambda c=c: group.port(c))
+        group.gens = [r.run_iter() for r in runners]
+        while not all(group.done):
+            for c in range(group.K):
+                if not group.done[c]:
+                    group.advance(c)
+    finally:
+        for r in runners:
+            r.__dict__.pop("_fused_dense", None)
+        for g in group.gens or ():
+            g.close()

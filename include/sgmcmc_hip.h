@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGMCMC_ABI_VERSION 11
+#define SGMCMC_ABI_VERSION 12
 #define SGMCMC_CHUNK 4096 /* default elements per arena chunk = 256 threads x 4 items x 4 elements */
 #define SGMCMC_CHUNK_SMALL 1024 /* small models: one item per thread, 4x more workgroups */
 #define SGMCMC_NSUMS 6
@@ -405,6 +405,17 @@ typedef struct {
 int sgmcmc_dense_step_multi(const sgmcmc_dense_chain* chains_dev, const sgmcmc_dense_chain* chain0_host, int n_chains,
                             const sgmcmc_step_args* A, const uint16_t* idx_host, const sgmcmc_step_args* A_pending,
                             void* stream);
+/* The same for chains that do NOT share a schedule (a temperature ladder, a sweep over step sizes): where
+ * sgmcmc_dense_step_multi takes ONE block of scalars for all chains, this takes `A`: [n_chains] blocks and `A_pending`:
+ * [n_chains] blocks (or NULL), chain c stepping with A[c] and finalizing A_pending[c]; both arrays travel by value in
+ * the kernel arguments (8 x 128 B).  Per chain: num_data, b2h2, bh, bhn, mom_decay, grad_v, noise_std (0 = that chain
+ * does not draw), rmsprop_alpha, grad_clamp, seed.  One per launch -- hipErrorInvalidValue otherwise, checked on the
+ * host before anything is launched: kind, flags, the segment and chunk ranges and draw, of A and of A_pending (chains
+ * in lock-step share the sweep counter and the metric cadence).  A[c].stream is ignored as above.  Chain c's results
+ * are bit-identical to the same chain stepped alone. */
+int sgmcmc_dense_step_multi_args(const sgmcmc_dense_chain* chains_dev, const sgmcmc_dense_chain* chain0_host,
+                                 int n_chains, const sgmcmc_step_args* A, const uint16_t* idx_host,
+                                 const sgmcmc_step_args* A_pending, void* stream);
 
 /* The per-segment bookkeeping of a transition that was launched with SGMCMC_DEFER_FINALIZE. */
 int sgmcmc_finalize(const sgmcmc_layout* L, const sgmcmc_step_args* A, void* stream);
