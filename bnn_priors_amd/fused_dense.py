@@ -14,8 +14,10 @@ element-wise priors; reference models/dense_nets.py:48-67) a leapfrog step is
 captured once per batch size (by the library itself, on an internal stream:
 ``sgmcmc_dense_stepper_create``) and replayed with ONE native call per step that also ships the
 per-step scalars and row indices through a ring of pinned slots; metric steps read ONE buffer back.  Numerically
-the gradient differs from the autograd path only by fp32 summation order (tested against a
-PyTorch reference in tests/test_fused_dense.py); everything downstream is the same code.
+the gradient differs from the autograd path only by fp32 summation order (the one-launch kernel is tested against a
+PyTorch reference in tests/test_fused_dense.py; the routes a step actually takes -- the two-launch split, the inline
+one-launch kernels, the graph replicas, the multi-chain launches -- against a float64 gradient and, for the transition,
+bit for bit against the C oracle in tests/test_dense_step_reference.py); everything downstream is the same code.
 """
 import ctypes
 

@@ -6,7 +6,6 @@ the same chain run alone.
 Shapes are the smallest at which the kernels can go wrong: 16 input features (the kernels need ``in % 4 == 0``), hidden
 8 and 8, 4 classes; batches of 12 of 48 rows (one partial slice of MLP_ROWS = 16 rows, four batches per epoch), 10 of 50,
 and MLP_ROWS + 4 of 3 (MLP_ROWS + 4) rows (two slices, the last one partial)."""
-import collections
 import ctypes
 
 import numpy as np
@@ -14,73 +13,17 @@ import pytest
 import torch
 
 from bnn_priors_amd import _hip
+from dense_step_helpers import CLASSES, IN, LADDER, WIDTH, _begun, _Counting, _runner, _snapshot
 
-DEV = "cuda:0"
-IN, WIDTH, CLASSES = 16, 8, 4
 ROWS2 = _hip.MLP_ROWS + 4            # a batch of two slices, the second one partial
 INVALID = 1                          # hipErrorInvalidValue
 
 
-# ------------------------------------------------------------------ builders
-def _runner(c, kind="VerletSGLDReject", *, T=1.0, lr=0.01, mom=0.9, n=48, batch=12, prior="gaussian", width=WIDTH,
-            seed=None, loader_seed=None, **kw):
-    "runner ``c`` of the tiny dense classifier on its own synthetic device-resident set (not begun)"
-    from bnn_priors_amd import models
-    from bnn_priors_amd.inference_reject import runner_class
-    from bnn_priors_amd.storage import MemoryMetrics, MemoryModelSaver
-    g = torch.Generator().manual_seed(100 + c)
-    x = torch.rand(n + 8, IN, generator=g)
-    y = torch.randint(0, CLASSES, (n + 8,), generator=g)
-    mk = torch.utils.data.TensorDataset
-    lg = None if loader_seed is None else torch.Generator().manual_seed(loader_seed)
-    train = torch.utils.data.DataLoader(mk(x[:n].to(DEV), y[:n].to(DEV)), batch_size=batch, shuffle=True, generator=lg)
-    test = torch.utils.data.DataLoader(mk(x[n:].to(DEV), y[n:].to(DEV)), batch_size=8)
-    torch.manual_seed(10 + c)
-    model = models.get_model(x[:2], torch.tensor([0, CLASSES - 1]), "classificationdensenet", width=width, depth=3,
-                             weight_prior=prior, weight_scale=2 ** .5, bias_prior="gaussian", bias_scale=1.)
-    models.he_initialize(model)
-    run = dict(epochs_per_cycle=2, warmup_epochs=1, sample_epochs=1, skip=1, metrics_skip=10, cycles=1, precond_update=1,
-               sampling_decay="cosine")
-    run.update(kw)
-    return runner_class(kind)(model=model.to(DEV), dataloader=train, dataloader_test=test, learning_rate=lr,
-                              temperature=T, momentum=mom, metrics_saver=MemoryMetrics(), model_saver=MemoryModelSaver(),
-                              seed=(99 + c) if seed is None else seed, chain_id=c, **run)
-
-
-def _begun(*a, **kw):
-    r = _runner(*a, **kw)
-    r.begin()
-    f = r._fused_dense()
-    assert f is not None and f.direct and f.split
-    return r, f
-
-
-def _snapshot(runner):
-    opt = runner.optimizer
-    return ([p.detach().clone() for p in runner._params],
-            [opt.state[p]["momentum_buffer"].clone() for p in runner._params],
-            [opt.state[p]["square_avg"].clone() for p in runner._params])
-
-
+# ------------------------------------------------------------------ builders (shared: tests/dense_step_helpers.py)
 def _same(a, b, what):
     for part, u, v in zip(("theta", "momentum", "square_avg"), a, b):
         for i, (s, t) in enumerate(zip(u, v)):
             assert torch.equal(s, t), f"{what}: {part} of tensor {i} differs"
-
-
-class _Counting:
-    "the library with every call counted (a thin wrapper around the bound ctypes functions)"
-
-    def __init__(self, lib):
-        self._lib, self.calls = lib, collections.Counter()
-
-    def __getattr__(self, name):
-        fn = getattr(self._lib, name)
-
-        def call(*a):
-            self.calls[name] += 1
-            return fn(*a)
-        return call
 
 
 def _ladder_vs_twins(specs, steps, metric_steps, n=48, batch=12, expect="sgmcmc_dense_step_multi_args", batches=None):
@@ -117,7 +60,6 @@ def _ladder_vs_twins(specs, steps, metric_steps, n=48, batch=12, expect="sgmcmc_
     return chains
 
 
-LADDER = [dict(T=1.0, lr=0.01, mom=0.9), dict(T=0.1, lr=0.005, mom=0.5), dict(T=0.0, lr=0.02, mom=0.99)]
 
 gpu = pytest.mark.gpu
 
