@@ -18,6 +18,15 @@
 //           tensor like the sampler's noise index), per-workgroup loss / #correct.
 // The partials are summed over s in a fixed order by sgmcmc_grad_reduce_prior (no atomics:
 // run-to-run bitwise reproducible), which also adds the prior's gradient.
+//
+// Two kernel families run the same arithmetic: the one-launch kernel above (mlp_fwdbwd_body: 1024 threads, dynamic LDS)
+// and the two-launch split of the latency-critical leapfrog step (mlp_f1_body + mlp_rest_body: 256 threads, static LDS,
+// KSPLIT x more workgroups; further down).  Every phase -- forward 1's load block and MFMA chain, the layer-1 combine,
+// forward 2 / 3, the softmax cross-entropy, the dW3 / d2 / dW2 / d1 tiles, the bias sums, the dW1 tile pair with its
+// transposed store -- is ONE __device__ function on a struct of LDS pointers (MlpLds); a body decides which waves run
+// it, stages its arrays (the dynamic carve-up; the split's register-staged global loads) and places the barriers.  So
+// the routes give the same bits wherever a K quarter has at most F1_UNROLL steps
+// (tests/test_dense_step_reference.py::test_routes_agree_bit_for_bit).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -44,6 +53,233 @@ __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
 
 struct IdxBlock { int32_t idx[SGMCMC_MLP_MAX_INLINE]; };
 
+// ---------------------------------------------------------------- the phases, each written once
+// Both kernel families run these.  A phase is the arithmetic of one wave (or one thread) on the workgroup's LDS arrays;
+// WHO runs it (which waves, which workgroup of a slice), the barriers between phases and how the arrays were staged are
+// the caller's.  The library is built with -ffp-contract=off, so the order of operations written here is the result's
+// bits on every route: j ascending in every MFMA chain, acc0 / acc1 alternating in forward 1, rows ascending in the sums.
+// (r, g) = (lane & 15, lane >> 4) are the MFMA fragment coordinates, nt / mt a 16-wide column / row tile.
+struct MlpLds {
+  float *h1s, *h2s;  // [ROWS][HS]  relu(layer 1), relu(layer 2)
+  float *d1s, *d2s;  // [ROWS][HS]  dL/d(pre-activation 1), dL/d(pre-activation 2)
+  float *lgs, *dfs;  // [ROWS][OP]  logits, dL/dlogits
+  float* red;        // [2][ROWS]   per-row loss / correct
+  float *w2s, *w3s;  // [HP][HS], [OP][HS]  W2, W3, zero padded
+  float* bs;         // [3][HP]     b1, b2, b3 (zero padded)
+  int* ys;           // [ROWS]      labels (-1 = padding row)
+  float* patch;      // [16][STG]   THIS wave's store-staging patch
+};
+
+// forward 1, one block of <= F1_UNROLL K steps from step jb on, in two halves so that a caller can put its own staging
+// between them: every W1 load of the lane is issued (W1 was just rewritten by the sampler kernel on other XCDs: these
+// are long-latency reads) ...
+__device__ __forceinline__ void mlp_f1_load(float4 (&w)[F1_UNROLL], const float* __restrict__ wrow, bool live, int jb,
+                                            int j1, int g, int IN) {
+#pragma unroll
+  for (int u = 0; u < F1_UNROLL; ++u) {
+    const int k = 16 * (jb + u) + 4 * g;
+    w[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (live && jb + u < j1 && k < IN) w[u] = *reinterpret_cast<const float4*>(wrow + k);
+  }
+}
+// ... then the MFMA chain on two accumulators; xrow: this lane's four inputs of step jb (row r, columns 16 jb + 4 g ..)
+__device__ __forceinline__ void mlp_f1_chain(const float4 (&w)[F1_UNROLL], const float* xrow, int jb, int j1,
+                                             f32x4& acc0, f32x4& acc1) {
+#pragma unroll
+  for (int u = 0; u < F1_UNROLL; ++u) {
+    if (jb + u < j1) {
+      const float4 a = *reinterpret_cast<const float4*>(xrow + 16 * u);
+      acc0 = mfma4(a.x, w[u].x, acc0);
+      acc1 = mfma4(a.y, w[u].y, acc1);
+      acc0 = mfma4(a.z, w[u].z, acc0);
+      acc1 = mfma4(a.w, w[u].w, acc1);
+    }
+  }
+}
+
+// h1[row][n] = relu(b1 + the four K-quarter partials, in this order)
+__device__ __forceinline__ void mlp_combine1(const MlpLds& S, int H1, int row, int n, float q0, float q1, float q2,
+                                             float q3) {
+  float pre = S.bs[n];
+  pre += q0;
+  pre += q1;
+  pre += q2;
+  pre += q3;
+  S.h1s[row * HS + n] = (n < H1 && pre > 0.f) ? pre : 0.f;
+}
+
+// forward 2: h2 = relu(h1 W2^T + b2), column tile nt
+__device__ __forceinline__ void mlp_forward2(const MlpLds& S, int H2, int nt, int r, int g) {
+  const int n = 16 * nt + r;
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int j = 0; j < HP / 4; ++j) {
+    const int k = 4 * j + g;
+    acc = mfma4(S.h1s[r * HS + k], S.w2s[n * HS + k], acc);
+  }
+  const float bias = S.bs[HP + n];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const float pre = acc[i] + bias;
+    S.h2s[(4 * g + i) * HS + n] = (n < H2 && pre > 0.f) ? pre : 0.f;
+  }
+}
+
+// forward 3: logits = h2 W3^T + b3 (one tile)
+__device__ __forceinline__ void mlp_forward3(const MlpLds& S, int r, int g) {
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int j = 0; j < HP / 4; ++j) {
+    const int k = 4 * j + g;
+    acc = mfma4(S.h2s[r * HS + k], S.w3s[r * HS + k], acc);
+  }
+  const float bias = S.bs[2 * HP + r];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) S.lgs[(4 * g + i) * OP + r] = acc[i] + bias;
+}
+
+// softmax cross-entropy, mean over the FULL batch (models/base.py:57-62,181-182):
+//   loss_i = logsumexp(f_i) - f_i[y_i];  dL/df = (softmax - onehot) / B.
+// Thread t of 256 owns logit (row, c) = (t >> 4, t & 15); 16-lane groups reduce with shuffles.
+__device__ __forceinline__ void mlp_softmax_ce(const MlpLds& S, int OUT, float st, float invB, int t) {
+  const int row = t >> 4, c = t & 15;
+  const int y = S.ys[row];
+  const float v = c < OUT ? S.lgs[row * OP + c] * st : -INFINITY;
+  float m = v;
+  int arg = c;
+#pragma unroll
+  for (int off = 8; off > 0; off >>= 1) {
+    const float om = __shfl_xor(m, off, 16);
+    const int oa = __shfl_xor(arg, off, 16);
+    if (om > m || (om == m && oa < arg)) { m = om; arg = oa; }  // first maximal index
+  }
+  float se = c < OUT ? expf(v - m) : 0.f;
+#pragma unroll
+  for (int off = 8; off > 0; off >>= 1) se += __shfl_xor(se, off, 16);
+  const float lse = m + logf(se);
+  float d = 0.f;
+  if (y >= 0 && c < OUT) d = (expf(v - lse) - (c == y ? 1.f : 0.f)) * invB * st;
+  S.dfs[row * OP + c] = d;
+  if (c == 0) {
+    S.red[row] = y >= 0 ? lse - S.lgs[row * OP + y] * st : 0.f;
+    S.red[ROWS + row] = (y >= 0 && arg == y) ? 1.f : 0.f;
+  }
+}
+// ... and the slice's loss / #correct, rows ascending (one thread)
+__device__ __forceinline__ void mlp_loss_sums(const MlpLds& S, float* loss, float* correct) {
+  float l = 0.f, c = 0.f;
+  for (int i = 0; i < ROWS; ++i) { l += S.red[i]; c += S.red[ROWS + i]; }
+  *loss = l;
+  *correct = c;
+}
+
+// a bias gradient: column `col` of a [ROWS][stride] array summed over the rows, ascending
+__device__ __forceinline__ float mlp_column_sum(const float* a, int stride, int col) {
+  float s = 0.f;
+  for (int i = 0; i < ROWS; ++i) s += a[i * stride + col];
+  return s;
+}
+
+// the A fragments of a weight-gradient tile: d^T for row tile m0 of d1s / d2s, one value per K step (4 batch rows)
+__device__ __forceinline__ void mlp_dT_fragment(float (&a)[ROWS / 4], const float* d, int m0, int r, int g) {
+#pragma unroll
+  for (int j = 0; j < ROWS / 4; ++j) a[j] = d[(4 * j + g) * HS + m0 + r];
+}
+
+// backward 3: dW3 = df^T h2, column tile nt
+__device__ __forceinline__ void mlp_dW3_tile(const MlpLds& S, float* __restrict__ gW3, int OUT, int H2, int nt, int r,
+                                             int g) {
+  const int n = 16 * nt + r;  // h2 unit
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int j = 0; j < ROWS / 4; ++j) {
+    const int k = 4 * j + g;  // batch row
+    acc = mfma4(S.dfs[k * OP + r], S.h2s[k * HS + n], acc);
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int m = 4 * g + i;  // output class
+    if (m < OUT && n < H2) gW3[m * H2 + n] = acc[i];
+  }
+}
+// ... and d2 = (df W3) * [h2 > 0], column tile nt
+__device__ __forceinline__ void mlp_backward3_d2(const MlpLds& S, int nt, int r, int g) {
+  const int n = 16 * nt + r;
+  f32x4 dacc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int j = 0; j < OP / 4; ++j) {
+    const int k = 4 * j + g;  // class
+    dacc = mfma4(S.dfs[r * OP + k], S.w3s[k * HS + n], dacc);
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int row = 4 * g + i;
+    S.d2s[row * HS + n] = S.h2s[row * HS + n] > 0.f ? dacc[i] : 0.f;
+  }
+}
+
+// backward 2: dW2 = d2^T h1, tile (row tile m0 whose fragments are `a`, column tile nt)
+__device__ __forceinline__ void mlp_dW2_tile(const MlpLds& S, const float (&a)[ROWS / 4], float* __restrict__ gW2,
+                                             int H1, int H2, int m0, int nt, int r, int g) {
+  const int n = 16 * nt + r;  // h1 unit
+  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int j = 0; j < ROWS / 4; ++j) acc = mfma4(a[j], S.h1s[(4 * j + g) * HS + n], acc);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int m = m0 + 4 * g + i;
+    if (m < H2 && n < H1) gW2[m * H1 + n] = acc[i];
+  }
+}
+// ... and d1 = (d2 W2) * [h1 > 0], column tile nt
+__device__ __forceinline__ void mlp_backward2_d1(const MlpLds& S, int nt, int r, int g) {
+  const int n = 16 * nt + r;
+  f32x4 dacc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int j = 0; j < HP / 4; ++j) {
+    const int k = 4 * j + g;  // h2 unit
+    dacc = mfma4(S.d2s[r * HS + k], S.w2s[k * HS + n], dacc);
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int row = 4 * g + i;
+    S.d1s[row * HS + n] = S.h1s[row * HS + n] > 0.f ? dacc[i] : 0.f;
+  }
+}
+
+// backward 1: dW1 = d1^T x for row tile m0 (fragments `a`) and the input-column tiles t0 and, if `two`, t1 of the
+// [ROWS][xstride] slice xs, whose column 0 is input column col0.  Each 16x16 result is transposed through the wave's LDS
+// patch so that the store is one 16-byte access per lane (4 lanes cover a 64-byte row segment).
+__device__ __forceinline__ void mlp_dW1_pair(const MlpLds& S, const float (&a)[ROWS / 4], const float* xs, int xstride,
+                                             int t0, int t1, bool two, int col0, float* __restrict__ gW1, int H1, int IN,
+                                             int m0, int lane) {
+  const int r = lane & 15, g = lane >> 4;
+  const int srow = lane >> 2, sc4 = (lane & 3) * 4;  // this lane's row / column group in the patch
+  f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int j = 0; j < ROWS / 4; ++j) {
+    const float* xr = xs + (4 * j + g) * xstride;
+    acc0 = mfma4(a[j], xr[16 * t0 + r], acc0);
+    if (two) acc1 = mfma4(a[j], xr[16 * t1 + r], acc1);
+  }
+#pragma unroll
+  for (int half = 0; half < 2; ++half) {
+    if (half == 1 && !two) break;
+    const f32x4 acc = half ? acc1 : acc0;
+    const int nb = col0 + 16 * (half ? t1 : t0);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) S.patch[(4 * g + i) * STG + r] = acc[i];
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    const float4 v = *reinterpret_cast<const float4*>(S.patch + srow * STG + sc4);
+    const int m = m0 + srow, col = nb + sc4;
+    if (m < H1 && col < IN) *reinterpret_cast<float4*>(gW1 + (int64_t)m * IN + col) = v;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
+// ---------------------------------------------------------------- the one-launch kernel
 template <bool INLINE>
 __device__ __forceinline__ void mlp_fwdbwd_body(const sgmcmc_mlp_args& P, const IdxBlock* IB) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -68,6 +304,7 @@ __device__ __forceinline__ void mlp_fwdbwd_body(const sgmcmc_mlp_args& P, const 
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 15, g = lane >> 4;  // MFMA fragment coordinates
+  const MlpLds lds = {h1s, h2s, d1s, d2s, lgs, dfs, red, w2s, w3s, bs, ys, stg + wave * 16 * STG};
   const int slice = blockIdx.x;
   const int row0 = slice * ROWS;
   float* __restrict__ gp = P.gpart + (int64_t)slice * P.gpart_stride;
@@ -115,9 +352,7 @@ __device__ __forceinline__ void mlp_fwdbwd_body(const sgmcmc_mlp_args& P, const 
   __syncthreads();
   MLP_TRACE();  // end of phase0
 
-  // ---- forward 1: h1 = relu(x W1^T + b1).  Wave (nt, q): hidden units 16nt..16nt+15, K quarter q;
-  //      all of a lane's W1 loads are issued before the first MFMA (W1 was just rewritten by the
-  //      sampler kernel on other XCDs, so these are long-latency reads).
+  // ---- forward 1: h1 = relu(x W1^T + b1).  Wave (nt, q): hidden units 16nt..16nt+15, K quarter q (partials in f1p)
   {
     const int nt = wave & 3, q = wave >> 2;
     const int n = 16 * nt + r;
@@ -128,22 +363,8 @@ __device__ __forceinline__ void mlp_fwdbwd_body(const sgmcmc_mlp_args& P, const 
     f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
     for (int jb = j0; jb < j1; jb += F1_UNROLL) {
       float4 b[F1_UNROLL];
-#pragma unroll
-      for (int u = 0; u < F1_UNROLL; ++u) {
-        const int k = 16 * (jb + u) + 4 * g;
-        b[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (live && jb + u < j1 && k < IN) b[u] = *reinterpret_cast<const float4*>(wrow + k);
-      }
-#pragma unroll
-      for (int u = 0; u < F1_UNROLL; ++u) {
-        if (jb + u < j1) {
-          const float4 a = *reinterpret_cast<const float4*>(xs + r * XS + 16 * (jb + u) + 4 * g);
-          acc0 = mfma4(a.x, b[u].x, acc0);
-          acc1 = mfma4(a.y, b[u].y, acc1);
-          acc0 = mfma4(a.z, b[u].z, acc0);
-          acc1 = mfma4(a.w, b[u].w, acc1);
-        }
-      }
+      mlp_f1_load(b, wrow, live, jb, j1, g, IN);
+      mlp_f1_chain(b, xs + r * XS + 16 * jb + 4 * g, jb, j1, acc0, acc1);
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) f1p[(q * ROWS + 4 * g + i) * HS + n] = acc0[i] + acc1[i];
@@ -151,198 +372,59 @@ __device__ __forceinline__ void mlp_fwdbwd_body(const sgmcmc_mlp_args& P, const 
   __syncthreads();
   for (int e = tid; e < ROWS * HP; e += kMlpThreads) {
     const int row = e / HP, n = e - row * HP;
-    float pre = bs[n];
-#pragma unroll
-    for (int q = 0; q < KSPLIT; ++q) pre += f1p[(q * ROWS + row) * HS + n];
-    h1s[row * HS + n] = (n < H1 && pre > 0.f) ? pre : 0.f;
+    const float* part = f1p + row * HS + n;
+    mlp_combine1(lds, H1, row, n, part[0], part[ROWS * HS], part[2 * ROWS * HS], part[3 * ROWS * HS]);
   }
   __syncthreads();
   MLP_TRACE();  // end of f1
 
-  // ---- forward 2: h2 = relu(h1 W2^T + b2)   (waves 0-3, one column tile each)
-  if (wave < 4) {
-    const int n = 16 * wave + r;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int j = 0; j < HP / 4; ++j) {
-      const int k = 4 * j + g;
-      acc = mfma4(h1s[r * HS + k], w2s[n * HS + k], acc);
-    }
-    const float bias = bs[HP + n];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float pre = acc[i] + bias;
-      h2s[(4 * g + i) * HS + n] = (n < H2 && pre > 0.f) ? pre : 0.f;
-    }
-  }
+  // ---- forward 2 (waves 0-3, one column tile each), forward 3 (one tile: wave 0)
+  if (wave < 4) mlp_forward2(lds, H2, wave, r, g);
   __syncthreads();
   MLP_TRACE();  // end of f2
-
-  // ---- forward 3: logits = h2 W3^T + b3 (one tile: wave 0)
-  if (wave == 0) {
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int j = 0; j < HP / 4; ++j) {
-      const int k = 4 * j + g;
-      acc = mfma4(h2s[r * HS + k], w3s[r * HS + k], acc);
-    }
-    const float bias = bs[2 * HP + r];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) lgs[(4 * g + i) * OP + r] = acc[i] + bias;
-  }
+  if (wave == 0) mlp_forward3(lds, r, g);
   __syncthreads();
   MLP_TRACE();  // end of f3
 
-  // ---- softmax cross-entropy, mean over the FULL batch (models/base.py:57-62,181-182):
-  //      loss_i = logsumexp(f_i) - f_i[y_i];  dL/df = (softmax - onehot) / B.
-  //      Thread (row, c) of the first 256 owns one logit; 16-lane groups reduce with shuffles.
-  if (tid < ROWS * OP) {
-    const int row = tid >> 4, c = tid & 15;
-    const int y = ys[row];
-    const float st = P.inv_softmax_temp;
-    const float v = c < OUT ? lgs[row * OP + c] * st : -INFINITY;
-    float m = v;
-    int arg = c;
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1) {
-      const float om = __shfl_xor(m, off, 16);
-      const int oa = __shfl_xor(arg, off, 16);
-      if (om > m || (om == m && oa < arg)) { m = om; arg = oa; }  // first maximal index
-    }
-    float e = c < OUT ? expf(v - m) : 0.f;
-    float se = e;
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1) se += __shfl_xor(se, off, 16);
-    const float lse = m + logf(se);
-    float d = 0.f;
-    if (y >= 0 && c < OUT) d = (expf(v - lse) - (c == y ? 1.f : 0.f)) * invB * st;
-    dfs[row * OP + c] = d;
-    if (c == 0) {
-      red[row] = y >= 0 ? lse - lgs[row * OP + y] * st : 0.f;
-      red[ROWS + row] = (y >= 0 && arg == y) ? 1.f : 0.f;
-    }
-  }
+  // ---- softmax cross-entropy: the first 256 threads own one logit each
+  if (tid < ROWS * OP) mlp_softmax_ce(lds, OUT, P.inv_softmax_temp, invB, tid);
   __syncthreads();
-  if (tid == 0) {
-    float l = 0.f, c = 0.f;
-    for (int i = 0; i < ROWS; ++i) { l += red[i]; c += red[ROWS + i]; }
-    P.loss_part[slice] = l;
-    P.correct_part[slice] = c;
-  }
+  if (tid == 0) mlp_loss_sums(lds, P.loss_part + slice, P.correct_part + slice);
   MLP_TRACE();  // end of softmax
 
-  // ---- backward 3: dW3 = df^T h2 (tile column w), db3, and d2 = (df W3) * [h2 > 0]
+  // ---- backward 3: dW3 and d2 (waves 0-3, one column tile each), db3 (wave 4)
   if (wave < 4) {
-    const int n = 16 * wave + r;  // h2 unit
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int j = 0; j < ROWS / 4; ++j) {
-      const int k = 4 * j + g;  // batch row
-      acc = mfma4(dfs[k * OP + r], h2s[k * HS + n], acc);
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int m = 4 * g + i;  // output class
-      if (m < OUT && n < H2) gp[P.off_W3 + m * H2 + n] = acc[i];
-    }
-    f32x4 dacc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int j = 0; j < OP / 4; ++j) {
-      const int k = 4 * j + g;  // class
-      dacc = mfma4(dfs[r * OP + k], w3s[k * HS + n], dacc);
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int row = 4 * g + i;
-      d2s[row * HS + n] = h2s[row * HS + n] > 0.f ? dacc[i] : 0.f;
-    }
+    mlp_dW3_tile(lds, gp + P.off_W3, OUT, H2, wave, r, g);
+    mlp_backward3_d2(lds, wave, r, g);
   } else if (wave == 4 && lane < OUT) {
-    float s = 0.f;
-    for (int i = 0; i < ROWS; ++i) s += dfs[i * OP + lane];
-    gp[P.off_b3 + lane] = s;
+    gp[P.off_b3 + lane] = mlp_column_sum(dfs, OP, lane);
   }
   __syncthreads();
   MLP_TRACE();  // end of b3
 
-  // ---- backward 2: dW2 = d2^T h1 (16 tiles: one per wave), db2, d1 = (d2 W2) * [h1 > 0]
+  // ---- backward 2: dW2 (16 tiles: one per wave), d1 (waves 0-3), db2 (wave 4)
   {
-    const int m0 = 16 * (wave & 3), n = 16 * (wave >> 2) + r;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int j = 0; j < ROWS / 4; ++j)
-      acc = mfma4(d2s[(4 * j + g) * HS + m0 + r], h1s[(4 * j + g) * HS + n], acc);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int m = m0 + 4 * g + i;
-      if (m < H2 && n < H1) gp[P.off_W2 + m * H1 + n] = acc[i];
-    }
+    float a[ROWS / 4];
+    mlp_dT_fragment(a, d2s, 16 * (wave & 3), r, g);
+    mlp_dW2_tile(lds, a, gp + P.off_W2, H1, H2, 16 * (wave & 3), wave >> 2, r, g);
   }
   if (wave < 4) {
-    const int n = 16 * wave + r;  // h1 unit
-    f32x4 dacc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int j = 0; j < HP / 4; ++j) {
-      const int k = 4 * j + g;  // h2 unit
-      dacc = mfma4(d2s[r * HS + k], w2s[k * HS + n], dacc);
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int row = 4 * g + i;
-      d1s[row * HS + n] = h1s[row * HS + n] > 0.f ? dacc[i] : 0.f;
-    }
+    mlp_backward2_d1(lds, wave, r, g);
   } else if (wave == 4 && lane < H2) {
-    float s = 0.f;
-    for (int i = 0; i < ROWS; ++i) s += d2s[i * HS + lane];
-    gp[P.off_b2 + lane] = s;
+    gp[P.off_b2 + lane] = mlp_column_sum(d2s, HS, lane);
   }
   __syncthreads();
   MLP_TRACE();  // end of b2
 
-  // ---- backward 1: dW1 = d1^T x.  Wave (mt, c): hidden-unit tile mt, input-column tiles
-  //      c, c+4, c+8, ...; each 16x16 result is transposed through a per-wave LDS patch so the
-  //      store is one 16-byte access per lane (4 lanes cover a 64-byte row segment).
+  // ---- backward 1: dW1.  Wave (mt, c): hidden-unit tile mt, input-column tiles c, c+4, c+8, ... two at a time;
+  //      db1 (wave 4)
   {
-    const int mt = wave & 3, c0 = wave >> 2;
-    const int m0 = 16 * mt;
+    const int m0 = 16 * (wave & 3), tiles = INp >> 4;
     float a[ROWS / 4];
-#pragma unroll
-    for (int j = 0; j < ROWS / 4; ++j) a[j] = d1s[(4 * j + g) * HS + m0 + r];
-    float* __restrict__ patch = stg + wave * 16 * STG;
-    const int tiles = INp >> 4;
-    const int srow = lane >> 2, sc4 = (lane & 3) * 4;  // this lane's row / column group in the patch
-    for (int t = c0; t < tiles; t += 2 * KSPLIT) {
-      const int t1 = t + KSPLIT;
-      const bool two = t1 < tiles;
-      const int n0 = 16 * t, n1 = 16 * t1;
-      f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int j = 0; j < ROWS / 4; ++j) {
-        const float* xr = xs + (4 * j + g) * XS;
-        acc0 = mfma4(a[j], xr[n0 + r], acc0);
-        if (two) acc1 = mfma4(a[j], xr[n1 + r], acc1);
-      }
-#pragma unroll
-      for (int half = 0; half < 2; ++half) {
-        if (half == 1 && !two) break;
-        const f32x4 acc = half ? acc1 : acc0;
-        const int nb = half ? n1 : n0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) patch[(4 * g + i) * STG + r] = acc[i];
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        const float4 v = *reinterpret_cast<const float4*>(patch + srow * STG + sc4);
-        const int m = m0 + srow, col = nb + sc4;
-        if (m < H1 && col < IN)
-          *reinterpret_cast<float4*>(gp + P.off_W1 + (int64_t)m * IN + col) = v;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-      }
-    }
-    if (wave == 4 && lane < H1) {
-      float s = 0.f;
-      for (int i = 0; i < ROWS; ++i) s += d1s[i * HS + lane];
-      gp[P.off_b1 + lane] = s;
-    }
+    mlp_dT_fragment(a, d1s, m0, r, g);
+    for (int t = wave >> 2; t < tiles; t += 2 * KSPLIT)
+      mlp_dW1_pair(lds, a, xs, XS, t, t + KSPLIT, t + KSPLIT < tiles, 0, gp + P.off_W1, H1, IN, m0, lane);
+    if (wave == 4 && lane < H1) gp[P.off_b1 + lane] = mlp_column_sum(d1s, HS, lane);
   }
   if (P.trace) __syncthreads();
   MLP_TRACE();  // end of b1
@@ -377,21 +459,45 @@ int64_t sgmcmc_mlp_lds_bytes(int in_features) {
          (int64_t)sizeof(int64_t) * ROWS + (int64_t)sizeof(int) * ROWS;
 }
 
+namespace {
+// the shapes the kernels are written for (batch bounds are each entry point's own); `split`: a K quarter of the first
+// layer must also fit the F1_UNROLL steps the two-launch split keeps in registers
+bool dense_shape_ok(const sgmcmc_mlp_args& m, bool split = false) {
+  if (m.batch <= 0 || m.in_features <= 0 || (m.in_features & 3) || m.hidden1 <= 0 || m.hidden1 > HP ||
+      m.hidden2 <= 0 || m.hidden2 > HP || m.out_features <= 0 || m.out_features > OP ||
+      sgmcmc_mlp_lds_bytes(m.in_features) > 160 * 1024)
+    return false;
+  const int steps16 = ((m.in_features + 15) & ~15) >> 4;
+  return !split || (steps16 + KSPLIT - 1) / KSPLIT <= F1_UNROLL;
+}
+
+// raise the dynamic-LDS limit of `kernels` to `lds` bytes when that is above `granted`, the caller's high-water mark
+// (ask for what is needed: static LDS counts against the same 160 KiB)
+hipError_t grant_dynamic_lds(std::initializer_list<const void*> kernels, int64_t lds, int64_t& granted) {
+  if (lds <= granted) return hipSuccess;
+  for (const void* k : kernels) {
+    const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  granted = lds;
+  return hipSuccess;
+}
+
+sgmcmc_grad_parts grad_parts_of(const sgmcmc_mlp_args& mlp, double num_data) {
+  sgmcmc_grad_parts G;
+  G.gpart = mlp.gpart; G.loss_part = mlp.loss_part; G.correct_part = mlp.correct_part;
+  G.stride = mlp.gpart_stride; G.num_data = num_data; G.n_slices = (mlp.batch + ROWS - 1) / ROWS; G.batch = mlp.batch;
+  return G;
+}
+}  // namespace
+
 int sgmcmc_mlp_fwdbwd(const sgmcmc_mlp_args* P, void* stream) {
   SGMCMC_FRESH_ERROR_STATE();
-  if (!P || P->batch <= 0 || P->in_features <= 0 || (P->in_features & 3)) return (int)hipErrorInvalidValue;
-  if (P->hidden1 <= 0 || P->hidden1 > HP || P->hidden2 <= 0 || P->hidden2 > HP ||
-      P->out_features <= 0 || P->out_features > OP)
-    return (int)hipErrorInvalidValue;
+  if (!P || !dense_shape_ok(*P)) return (int)hipErrorInvalidValue;
   const int64_t lds = sgmcmc_mlp_lds_bytes(P->in_features);
-  if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
-  static int64_t attr_bytes = 0;   // ask for what is needed: static LDS counts against the same 160 KiB
-  if (lds > attr_bytes) {
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_fwdbwd_kernel),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    attr_bytes = lds;
-  }
+  static int64_t granted = 0;
+  const hipError_t e = grant_dynamic_lds({reinterpret_cast<const void*>(mlp_fwdbwd_kernel)}, lds, granted);
+  if (e != hipSuccess) return (int)e;
   const int slices = (P->batch + ROWS - 1) / ROWS;
   SGMCMC_LAUNCH(mlp_fwdbwd_kernel, dim3((unsigned)slices), dim3(kMlpThreads), (size_t)lds,
                      (hipStream_t)stream, *P);
@@ -464,12 +570,7 @@ __device__ __forceinline__ void mlp_f1_body(const sgmcmc_mlp_args& P, const int3
   const bool live = n < H1;
   const float* __restrict__ wrow = P.W1 + (int64_t)(live ? n : 0) * IN;
   float4 w[F1_UNROLL];
-#pragma unroll
-  for (int u = 0; u < F1_UNROLL; ++u) {
-    const int k = c0 + 16 * u + 4 * g;
-    w[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (live && j0 + u < j1 && k < IN) w[u] = *reinterpret_cast<const float4*>(wrow + k);
-  }
+  mlp_f1_load(w, wrow, live, j0, j1, g, IN);
   float* __restrict__ xq = S.xq + ((int64_t)(slice * KSPLIT + q) * ROWS) * XQ;
 #pragma unroll
   for (int u = 0; u < XG; ++u) {
@@ -482,16 +583,7 @@ __device__ __forceinline__ void mlp_f1_body(const sgmcmc_mlp_args& P, const int3
   }
   __syncthreads();
   f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int u = 0; u < F1_UNROLL; ++u) {
-    if (j0 + u < j1) {
-      const float4 a = *reinterpret_cast<const float4*>(xs + r * XQS + 16 * u + 4 * g);
-      acc0 = mfma4(a.x, w[u].x, acc0);
-      acc1 = mfma4(a.y, w[u].y, acc1);
-      acc0 = mfma4(a.z, w[u].z, acc0);
-      acc1 = mfma4(a.w, w[u].w, acc1);
-    }
-  }
+  mlp_f1_chain(w, xs + r * XQS + 4 * g, j0, j1, acc0, acc1);
   float* __restrict__ hp = S.h1part + ((int64_t)(slice * KSPLIT + q) * ROWS) * HP;
 #pragma unroll
   for (int i = 0; i < 4; ++i) hp[(4 * g + i) * HP + n] = acc0[i] + acc1[i];
@@ -526,6 +618,7 @@ __device__ __forceinline__ void mlp_rest_body(const sgmcmc_mlp_args& P, const sg
   float* __restrict__ gp = P.gpart + (int64_t)slice * P.gpart_stride;
   const float invB = P.grad_scale > 0.f ? P.grad_scale : 1.0f / (float)P.batch;
   const bool lead = q == 0;  // writes the small gradients and the loss of the slice
+  const MlpLds lds = {h1s, h2s, d1s, d2s, lgs, dfs, red, w2s, w3s, bs, ys, stg + wave * 16 * STG};
 
   // ---- all input loads up front, in registers: K1's partials, the stashed x quarter, W2, W3
   constexpr int HPN = ROWS * HP / kSplitThreads;                                // 4
@@ -576,10 +669,7 @@ __device__ __forceinline__ void mlp_rest_body(const sgmcmc_mlp_args& P, const sg
 #pragma unroll
   for (int u = 0; u < HPN; ++u) {
     const int e = tid + u * kSplitThreads, row = e / HP, n = e - row * HP;
-    float pre = bs[n];
-#pragma unroll
-    for (int qq = 0; qq < KSPLIT; ++qq) pre += hpre[u][qq];
-    h1s[row * HS + n] = (n < H1 && pre > 0.f) ? pre : 0.f;
+    mlp_combine1(lds, H1, row, n, hpre[u][0], hpre[u][1], hpre[u][2], hpre[u][3]);
   }
 #pragma unroll
   for (int u = 0; u < W2N; ++u) {
@@ -600,160 +690,36 @@ __device__ __forceinline__ void mlp_rest_body(const sgmcmc_mlp_args& P, const sg
     }
   }
   __syncthreads();
-  {  // forward 2
-    const int n = 16 * wave + r;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int j = 0; j < HP / 4; ++j) acc = mfma4(h1s[r * HS + 4 * j + g], w2s[n * HS + 4 * j + g], acc);
-    const float bias = bs[HP + n];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float pre = acc[i] + bias;
-      h2s[(4 * g + i) * HS + n] = (n < H2 && pre > 0.f) ? pre : 0.f;
-    }
-  }
+  // ---- the middle, in every workgroup of the slice: wave = column tile
+  mlp_forward2(lds, H2, wave, r, g);
   __syncthreads();
-  if (wave == 0) {  // forward 3
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int j = 0; j < HP / 4; ++j) acc = mfma4(h2s[r * HS + 4 * j + g], w3s[r * HS + 4 * j + g], acc);
-    const float bias = bs[2 * HP + r];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) lgs[(4 * g + i) * OP + r] = acc[i] + bias;
-  }
+  if (wave == 0) mlp_forward3(lds, r, g);
   __syncthreads();
-  {  // softmax cross-entropy: thread (row, c) owns one logit (256 threads = 16 x 16)
-    const int row = tid >> 4, c = tid & 15;
-    const int y = ys[row];
-    const float st = P.inv_softmax_temp;
-    const float v = c < OUT ? lgs[row * OP + c] * st : -INFINITY;
-    float m = v;
-    int arg = c;
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1) {
-      const float om = __shfl_xor(m, off, 16);
-      const int oa = __shfl_xor(arg, off, 16);
-      if (om > m || (om == m && oa < arg)) { m = om; arg = oa; }
-    }
-    float se = c < OUT ? expf(v - m) : 0.f;
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1) se += __shfl_xor(se, off, 16);
-    const float lse = m + logf(se);
-    float d = 0.f;
-    if (y >= 0 && c < OUT) d = (expf(v - lse) - (c == y ? 1.f : 0.f)) * invB * st;
-    dfs[row * OP + c] = d;
-    if (c == 0) {
-      red[row] = y >= 0 ? lse - lgs[row * OP + y] * st : 0.f;
-      red[ROWS + row] = (y >= 0 && arg == y) ? 1.f : 0.f;
-    }
-  }
+  mlp_softmax_ce(lds, OUT, P.inv_softmax_temp, invB, tid);  // (256 threads = 16 x 16 logits)
   __syncthreads();
-  if (lead && tid == 0) {
-    float l = 0.f, c = 0.f;
-    for (int i = 0; i < ROWS; ++i) { l += red[i]; c += red[ROWS + i]; }
-    P.loss_part[slice] = l;
-    P.correct_part[slice] = c;
+  if (lead && tid == 0) mlp_loss_sums(lds, P.loss_part + slice, P.correct_part + slice);
+  if (lead) {
+    mlp_dW3_tile(lds, gp + P.off_W3, OUT, H2, wave, r, g);
+    if (tid < OUT) gp[P.off_b3 + tid] = mlp_column_sum(dfs, OP, tid);
   }
-  {  // backward 3
-    const int n = 16 * wave + r;
-    if (lead) {
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int j = 0; j < ROWS / 4; ++j) acc = mfma4(dfs[(4 * j + g) * OP + r], h2s[(4 * j + g) * HS + n], acc);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int m = 4 * g + i;
-        if (m < OUT && n < H2) gp[P.off_W3 + m * H2 + n] = acc[i];
-      }
-      if (tid < OUT) {
-        float s = 0.f;
-        for (int i = 0; i < ROWS; ++i) s += dfs[i * OP + tid];
-        gp[P.off_b3 + tid] = s;
-      }
-    }
-    f32x4 dacc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int j = 0; j < OP / 4; ++j) dacc = mfma4(dfs[r * OP + 4 * j + g], w3s[(4 * j + g) * HS + n], dacc);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int row = 4 * g + i;
-      d2s[row * HS + n] = h2s[row * HS + n] > 0.f ? dacc[i] : 0.f;
-    }
-  }
+  mlp_backward3_d2(lds, wave, r, g);
   __syncthreads();
-  {  // backward 2
-    if (lead) {
-      const int m0 = 16 * wave;
-      float a[ROWS / 4];
-#pragma unroll
-      for (int j = 0; j < ROWS / 4; ++j) a[j] = d2s[(4 * j + g) * HS + m0 + r];
-#pragma unroll
-      for (int t = 0; t < HP / 16; ++t) {
-        const int n = 16 * t + r;
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int j = 0; j < ROWS / 4; ++j) acc = mfma4(a[j], h1s[(4 * j + g) * HS + n], acc);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int m = m0 + 4 * g + i;
-          if (m < H2 && n < H1) gp[P.off_W2 + m * H1 + n] = acc[i];
-        }
-      }
-      if (tid < H2) {
-        float s = 0.f;
-        for (int i = 0; i < ROWS; ++i) s += d2s[i * HS + tid];
-        gp[P.off_b2 + tid] = s;
-      }
-    }
-    const int n = 16 * wave + r;
-    f32x4 dacc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int j = 0; j < HP / 4; ++j) dacc = mfma4(d2s[r * HS + 4 * j + g], w2s[(4 * j + g) * HS + n], dacc);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int row = 4 * g + i;
-      d1s[row * HS + n] = h1s[row * HS + n] > 0.f ? dacc[i] : 0.f;
-    }
-  }
-  __syncthreads();
-  if (lead && tid < H1) {
-    float s = 0.f;
-    for (int i = 0; i < ROWS; ++i) s += d1s[i * HS + tid];
-    gp[P.off_b1 + tid] = s;
-  }
-  {  // backward 1: this workgroup's quarter of the input columns; wave = hidden-unit tile
-    const int m0 = 16 * wave;
+  if (lead) {  // dW2: wave = row tile, all four column tiles
     float a[ROWS / 4];
+    mlp_dT_fragment(a, d2s, 16 * wave, r, g);
 #pragma unroll
-    for (int j = 0; j < ROWS / 4; ++j) a[j] = d1s[(4 * j + g) * HS + m0 + r];
-    float* __restrict__ patch = stg + wave * 16 * STG;
-    const int srow = lane >> 2, sc4 = (lane & 3) * 4;
+    for (int t = 0; t < HP / 16; ++t) mlp_dW2_tile(lds, a, gp + P.off_W2, H1, H2, 16 * wave, t, r, g);
+    if (tid < H2) gp[P.off_b2 + tid] = mlp_column_sum(d2s, HS, tid);
+  }
+  mlp_backward2_d1(lds, wave, r, g);
+  __syncthreads();
+  if (lead && tid < H1) gp[P.off_b1 + tid] = mlp_column_sum(d1s, HS, tid);
+  {  // backward 1: this workgroup's quarter of the input columns, two tiles at a time; wave = hidden-unit tile
+    float a[ROWS / 4];
+    mlp_dT_fragment(a, d1s, 16 * wave, r, g);
     const int tiles = j1 - j0;
-    for (int t = 0; t < tiles; t += 2) {
-      const bool two = t + 1 < tiles;
-      f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int j = 0; j < ROWS / 4; ++j) {
-        const float* xr = xs + (4 * j + g) * XQS;
-        acc0 = mfma4(a[j], xr[16 * t + r], acc0);
-        if (two) acc1 = mfma4(a[j], xr[16 * (t + 1) + r], acc1);
-      }
-#pragma unroll
-      for (int half = 0; half < 2; ++half) {
-        if (half == 1 && !two) break;
-        const f32x4 acc = half ? acc1 : acc0;
-        const int nb = c0 + 16 * (t + half);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) patch[(4 * g + i) * STG + r] = acc[i];
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        const float4 v = *reinterpret_cast<const float4*>(patch + srow * STG + sc4);
-        const int m = m0 + srow, col = nb + sc4;
-        if (m < H1 && col < IN) *reinterpret_cast<float4*>(gp + P.off_W1 + (int64_t)m * IN + col) = v;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-      }
-    }
+    for (int t = 0; t < tiles; t += 2)
+      mlp_dW1_pair(lds, a, xs, XQS, t, t + 1, t + 1 < tiles, c0, gp + P.off_W1, H1, IN, 16 * wave, lane);
   }
 }
 
@@ -777,8 +743,9 @@ __global__ __launch_bounds__(kSplitThreads) void mlp_f1_multi_kernel(const sgmcm
   mlp_f1_body(P, nullptr, IM.idx[c]);
 }
 
-__global__ __launch_bounds__(kSplitThreads) void mlp_rest_multi_kernel(const sgmcmc_dense_chain* __restrict__ T,
-                                                                       sgmcmc_step_args Aprev, int with_finalize) {
+// chain blockIdx.y of the table with ITS block of transition scalars (the deferred finalize's), wherever that came from
+__device__ __forceinline__ void mlp_rest_chain(const sgmcmc_dense_chain* __restrict__ T, sgmcmc_step_args Aprev,
+                                               int with_finalize) {
   const int c = blockIdx.y;
   const sgmcmc_mlp_args P = T[c].mlp;
   const sgmcmc_layout L = T[c].layout;
@@ -786,10 +753,14 @@ __global__ __launch_bounds__(kSplitThreads) void mlp_rest_multi_kernel(const sgm
   mlp_rest_body(P, L, Aprev, with_finalize);
 }
 
+__global__ __launch_bounds__(kSplitThreads) void mlp_rest_multi_kernel(const sgmcmc_dense_chain* __restrict__ T,
+                                                                       sgmcmc_step_args Aprev, int with_finalize) {
+  mlp_rest_chain(T, Aprev, with_finalize);
+}
+
 extern "C++" {
 template <int KIND>
-__global__ __launch_bounds__(kThreads) void step_parts_multi_kernel(const sgmcmc_dense_chain* __restrict__ T,
-                                                                    sgmcmc_step_args A) {
+__device__ __forceinline__ void step_parts_chain(const sgmcmc_dense_chain* __restrict__ T, sgmcmc_step_args A) {
   const int c = blockIdx.y;
   const sgmcmc_layout L = T[c].layout;
   const sgmcmc_mlp_args& M = T[c].mlp;
@@ -798,6 +769,12 @@ __global__ __launch_bounds__(kThreads) void step_parts_multi_kernel(const sgmcmc
   A.stream = T[c].chain_id;
   const Early<float, 1> E = step_early<float, true, 1>(L, A.chunk_begin);
   step_body<float, KIND, true, 1, true, false, false, true>(L, A, G, &E);
+}
+
+template <int KIND>
+__global__ __launch_bounds__(kThreads) void step_parts_multi_kernel(const sgmcmc_dense_chain* __restrict__ T,
+                                                                    sgmcmc_step_args A) {
+  step_parts_chain<KIND>(T, A);
 }
 
 // ---- the same launches with EACH chain's own transition scalars (a temperature ladder, a step-size sweep): chain c
@@ -809,26 +786,13 @@ struct ArgsMulti { sgmcmc_step_args a[SGMCMC_MAX_CHAINS]; };
 template <int KIND>
 __global__ __launch_bounds__(kThreads) void step_parts_multi_args_kernel(const sgmcmc_dense_chain* __restrict__ T,
                                                                          ArgsMulti AM) {
-  const int c = blockIdx.y;
-  const sgmcmc_layout L = T[c].layout;
-  const sgmcmc_mlp_args& M = T[c].mlp;
-  const int slices = (M.batch + ROWS - 1) / ROWS;
-  const GradParts G = {M.gpart, slices, M.gpart_stride, M.loss_part, M.correct_part, M.batch, T[c].num_data};
-  sgmcmc_step_args A = AM.a[c];
-  A.stream = T[c].chain_id;
-  const Early<float, 1> E = step_early<float, true, 1>(L, A.chunk_begin);
-  step_body<float, KIND, true, 1, true, false, false, true>(L, A, G, &E);
+  step_parts_chain<KIND>(T, AM.a[blockIdx.y]);
 }
 }  // extern "C++"
 
 __global__ __launch_bounds__(kSplitThreads) void mlp_rest_multi_args_kernel(const sgmcmc_dense_chain* __restrict__ T,
                                                                             ArgsMulti AM, int with_finalize) {
-  const int c = blockIdx.y;
-  const sgmcmc_mlp_args P = T[c].mlp;
-  const sgmcmc_layout L = T[c].layout;
-  sgmcmc_step_args Aprev = AM.a[c];
-  Aprev.stream = T[c].chain_id;
-  mlp_rest_body(P, L, Aprev, with_finalize);
+  mlp_rest_chain(T, AM.a[blockIdx.y], with_finalize);
 }
 }  // namespace
 
@@ -844,27 +808,19 @@ int sgmcmc_dense_step_direct(const sgmcmc_layout* L, const sgmcmc_mlp_args* mlp,
                              const sgmcmc_step_args* A, double num_data, const int64_t* idx_host,
                              const sgmcmc_step_args* A_pending, void* stream) {
   SGMCMC_FRESH_ERROR_STATE();
-  if (!L || !mlp || !A || !idx_host || mlp->batch <= 0 || mlp->batch > SGMCMC_MLP_MAX_INLINE)
-    return (int)hipErrorInvalidValue;
-  if ((mlp->in_features & 3) || mlp->hidden1 > HP || mlp->hidden2 > HP || mlp->out_features > OP)
+  if (!L || !mlp || !A || !idx_host || mlp->batch > SGMCMC_MLP_MAX_INLINE || !dense_shape_ok(*mlp))
     return (int)hipErrorInvalidValue;
   if (A_pending && !(A_pending->flags & SGMCMC_SMALL_FINALIZE)) return (int)hipErrorInvalidValue;
-  const size_t lds = (size_t)sgmcmc_mlp_lds_bytes(mlp->in_features);
-  static size_t attr_bytes = 0;    // ask for what is needed: static LDS counts against the same 160 KiB
-  if (lds > attr_bytes) {
-    for (const void* k : {reinterpret_cast<const void*>(mlp_fwdbwd_kernel_inline),
-                          reinterpret_cast<const void*>(mlp_fwdbwd_kernel_inline_fin)}) {
-      const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return (int)e;
-    }
-    attr_bytes = lds;
-  }
+  const int64_t lds = sgmcmc_mlp_lds_bytes(mlp->in_features);
+  static int64_t granted = 0;
+  const hipError_t e = grant_dynamic_lds({reinterpret_cast<const void*>(mlp_fwdbwd_kernel_inline),
+                                          reinterpret_cast<const void*>(mlp_fwdbwd_kernel_inline_fin)}, lds, granted);
+  if (e != hipSuccess) return (int)e;
   IdxBlock IB;
   for (int b = 0; b < mlp->batch; ++b) IB.idx[b] = (int32_t)idx_host[b];
   const int slices = (mlp->batch + ROWS - 1) / ROWS;
   hipStream_t s = (hipStream_t)stream;
-  const int steps16 = ((mlp->in_features + 15) & ~15) >> 4;
-  if (mlp->split_scratch && (steps16 + KSPLIT - 1) / KSPLIT <= F1_UNROLL) {
+  if (mlp->split_scratch && dense_shape_ok(*mlp, true)) {
     sgmcmc_step_args Ap = A_pending ? *A_pending : *A;
     Ap.flags &= ~(uint32_t)SGMCMC_DEFER_FINALIZE;
     SGMCMC_LAUNCH(mlp_f1_kernel, dim3((unsigned)(slices * KSPLIT)), dim3(kSplitThreads), 0, s, *mlp, IB);
@@ -874,66 +830,85 @@ int sgmcmc_dense_step_direct(const sgmcmc_layout* L, const sgmcmc_mlp_args* mlp,
     sgmcmc_step_args Ap = *A_pending;
     Ap.flags &= ~(uint32_t)SGMCMC_DEFER_FINALIZE;
     SGMCMC_LAUNCH(mlp_fwdbwd_kernel_inline_fin, dim3((unsigned)slices + 1), dim3(kMlpThreads),
-                       lds, s, *mlp, IB, *L, Ap);
+                       (size_t)lds, s, *mlp, IB, *L, Ap);
   } else {
-    SGMCMC_LAUNCH(mlp_fwdbwd_kernel_inline, dim3((unsigned)slices), dim3(kMlpThreads), lds, s,
+    SGMCMC_LAUNCH(mlp_fwdbwd_kernel_inline, dim3((unsigned)slices), dim3(kMlpThreads), (size_t)lds, s,
                        *mlp, IB);
   }
-  sgmcmc_grad_parts G;
-  G.gpart = mlp->gpart; G.loss_part = mlp->loss_part; G.correct_part = mlp->correct_part;
-  G.stride = mlp->gpart_stride; G.num_data = num_data; G.n_slices = slices; G.batch = mlp->batch;
+  const sgmcmc_grad_parts G = grad_parts_of(*mlp, num_data);
   return sgmcmc_step_parts_value(L, A, &G, s);
 }
+
+namespace {
+// what both multi-chain entry points require of chain 0's record and of the (first) block
+bool dense_multi_ok(const sgmcmc_dense_chain* chains_dev, const sgmcmc_dense_chain* chain0_host, int n_chains,
+                    const sgmcmc_step_args* A, const uint16_t* idx_host) {
+  if (!chains_dev || !chain0_host || !A || !idx_host || n_chains <= 0 || n_chains > SGMCMC_MAX_CHAINS) return false;
+  const sgmcmc_mlp_args& mlp = chain0_host->mlp;
+  const sgmcmc_layout& L = chain0_host->layout;
+  return mlp.batch <= SGMCMC_MLP_BATCH_MULTI && mlp.split_scratch && dense_shape_ok(mlp, true) &&
+         L.dtype == SGMCMC_F32 && L.chunk_elems == SGMCMC_CHUNK_SMALL && !(A->flags & SGMCMC_UNALIGNED) &&
+         (A->flags & SGMCMC_SMALL_FINALIZE) && (A->flags & SGMCMC_DEFER_FINALIZE);
+}
+
+void fill_idx_multi(IdxMulti& IM, const uint16_t* idx_host, int n_chains, int batch) {
+  for (int c = 0; c < n_chains; ++c)
+    for (int b = 0; b < batch; ++b) IM.idx[c][b] = idx_host[(size_t)c * batch + b];
+}
+
+// the three launches of a lock-step step, after the entry point's validation.  A / A_pending: ONE block for all chains
+// (the 128-byte kernel argument), or with `per_chain` n_chains blocks each
+int dense_step_multi_launch(const sgmcmc_dense_chain* chains_dev, const sgmcmc_mlp_args& mlp, int n_chains,
+                            const sgmcmc_step_args* A, const uint16_t* idx_host, const sgmcmc_step_args* A_pending,
+                            bool per_chain, hipStream_t s) {
+  if (A->kind != SGMCMC_VERLET && A->kind != SGMCMC_HMC && A->kind != SGMCMC_SGLD) return (int)hipErrorInvalidValue;
+  IdxMulti IM;
+  fill_idx_multi(IM, idx_host, n_chains, mlp.batch);
+  ArgsMulti AM, AP;  // [0] alone when one block serves all chains (unused rows repeat chain 0: no uninitialised kernel argument)
+  for (int c = 0; c < SGMCMC_MAX_CHAINS; ++c) {
+    const int k = per_chain && c < n_chains ? c : 0;
+    AM.a[c] = A[k];
+    AP.a[c] = A_pending ? A_pending[k] : A[k];
+    AP.a[c].flags &= ~(uint32_t)SGMCMC_DEFER_FINALIZE;
+  }
+  const int slices = (mlp.batch + ROWS - 1) / ROWS, fin = A_pending ? 1 : 0;
+  const unsigned ny = (unsigned)n_chains;
+  const dim3 split(kSplitThreads), rest_grid((unsigned)(slices * KSPLIT + fin), ny);
+  SGMCMC_LAUNCH(mlp_f1_multi_kernel, dim3((unsigned)(slices * KSPLIT), ny), split, 0, s, chains_dev, IM);
+  if (per_chain)
+    SGMCMC_LAUNCH(mlp_rest_multi_args_kernel, rest_grid, split, 0, s, chains_dev, AP, fin);
+  else
+    SGMCMC_LAUNCH(mlp_rest_multi_kernel, rest_grid, split, 0, s, chains_dev, AP.a[0], fin);
+  const dim3 grid((unsigned)(A->chunk_end - A->chunk_begin), ny), block(kThreads);
+#define STEP_PARTS_MULTI(KIND)                                                                         \
+  if (per_chain)                                                                                       \
+    SGMCMC_LAUNCH(step_parts_multi_args_kernel<KIND>, grid, block, 0, s, chains_dev, AM);              \
+  else                                                                                                 \
+    SGMCMC_LAUNCH(step_parts_multi_kernel<KIND>, grid, block, 0, s, chains_dev, AM.a[0])
+  switch (A->kind) {
+    case SGMCMC_VERLET: STEP_PARTS_MULTI(SGMCMC_VERLET); break;
+    case SGMCMC_HMC: STEP_PARTS_MULTI(SGMCMC_HMC); break;
+    default: STEP_PARTS_MULTI(SGMCMC_SGLD); break;
+  }
+#undef STEP_PARTS_MULTI
+  return (int)hipGetLastError();
+}
+}  // namespace
 
 int sgmcmc_dense_step_multi(const sgmcmc_dense_chain* chains_dev, const sgmcmc_dense_chain* chain0_host, int n_chains,
                             const sgmcmc_step_args* A, const uint16_t* idx_host, const sgmcmc_step_args* A_pending,
                             void* stream) {
   SGMCMC_FRESH_ERROR_STATE();
-  if (!chains_dev || !chain0_host || !A || !idx_host || n_chains <= 0 || n_chains > SGMCMC_MAX_CHAINS)
-    return (int)hipErrorInvalidValue;
-  const sgmcmc_mlp_args& mlp = chain0_host->mlp;
-  const sgmcmc_layout& L = chain0_host->layout;
-  if (mlp.batch <= 0 || mlp.batch > SGMCMC_MLP_BATCH_MULTI || (mlp.in_features & 3) || mlp.hidden1 > HP ||
-      mlp.hidden2 > HP || mlp.out_features > OP || !mlp.split_scratch || L.dtype != SGMCMC_F32 ||
-      L.chunk_elems != SGMCMC_CHUNK_SMALL || (A->flags & SGMCMC_UNALIGNED) || !(A->flags & SGMCMC_SMALL_FINALIZE) ||
-      !(A->flags & SGMCMC_DEFER_FINALIZE))
-    return (int)hipErrorInvalidValue;
-  const int steps16 = ((mlp.in_features + 15) & ~15) >> 4;
-  if ((steps16 + KSPLIT - 1) / KSPLIT > F1_UNROLL) return (int)hipErrorInvalidValue;
-  IdxMulti IM;
-  for (int c = 0; c < n_chains; ++c)
-    for (int b = 0; b < mlp.batch; ++b) IM.idx[c][b] = idx_host[(size_t)c * mlp.batch + b];
-  const int slices = (mlp.batch + ROWS - 1) / ROWS;
-  hipStream_t s = (hipStream_t)stream;
-  sgmcmc_step_args Ap = A_pending ? *A_pending : *A;
-  Ap.flags &= ~(uint32_t)SGMCMC_DEFER_FINALIZE;
-  const unsigned ny = (unsigned)n_chains;
-  SGMCMC_LAUNCH(mlp_f1_multi_kernel, dim3((unsigned)(slices * KSPLIT), ny), dim3(kSplitThreads), 0, s, chains_dev, IM);
-  SGMCMC_LAUNCH(mlp_rest_multi_kernel, dim3((unsigned)(slices * KSPLIT + (A_pending ? 1 : 0)), ny), dim3(kSplitThreads),
-                0, s, chains_dev, Ap, A_pending ? 1 : 0);
-  const dim3 grid((unsigned)(A->chunk_end - A->chunk_begin), ny), block(kThreads);
-  switch (A->kind) {
-    case SGMCMC_VERLET: SGMCMC_LAUNCH(step_parts_multi_kernel<SGMCMC_VERLET>, grid, block, 0, s, chains_dev, *A); break;
-    case SGMCMC_HMC: SGMCMC_LAUNCH(step_parts_multi_kernel<SGMCMC_HMC>, grid, block, 0, s, chains_dev, *A); break;
-    case SGMCMC_SGLD: SGMCMC_LAUNCH(step_parts_multi_kernel<SGMCMC_SGLD>, grid, block, 0, s, chains_dev, *A); break;
-    default: return (int)hipErrorInvalidValue;
-  }
-  return (int)hipGetLastError();
+  if (!dense_multi_ok(chains_dev, chain0_host, n_chains, A, idx_host)) return (int)hipErrorInvalidValue;
+  return dense_step_multi_launch(chains_dev, chain0_host->mlp, n_chains, A, idx_host, A_pending, false,
+                                 (hipStream_t)stream);
 }
 
 int sgmcmc_dense_step_multi_args(const sgmcmc_dense_chain* chains_dev, const sgmcmc_dense_chain* chain0_host,
                                  int n_chains, const sgmcmc_step_args* A, const uint16_t* idx_host,
                                  const sgmcmc_step_args* A_pending, void* stream) {
   // host-side validation first: nothing below touches the runtime before the blocks are known to agree
-  if (!chains_dev || !chain0_host || !A || !idx_host || n_chains <= 0 || n_chains > SGMCMC_MAX_CHAINS)
-    return (int)hipErrorInvalidValue;
-  const sgmcmc_mlp_args& mlp = chain0_host->mlp;
-  const sgmcmc_layout& L = chain0_host->layout;
-  if (mlp.batch <= 0 || mlp.batch > SGMCMC_MLP_BATCH_MULTI || (mlp.in_features & 3) || mlp.hidden1 > HP ||
-      mlp.hidden2 > HP || mlp.out_features > OP || !mlp.split_scratch || L.dtype != SGMCMC_F32 ||
-      L.chunk_elems != SGMCMC_CHUNK_SMALL || (A->flags & SGMCMC_UNALIGNED) || !(A->flags & SGMCMC_SMALL_FINALIZE) ||
-      !(A->flags & SGMCMC_DEFER_FINALIZE))
-    return (int)hipErrorInvalidValue;
+  if (!dense_multi_ok(chains_dev, chain0_host, n_chains, A, idx_host)) return (int)hipErrorInvalidValue;
   if (A->kind != SGMCMC_VERLET && A->kind != SGMCMC_HMC && A->kind != SGMCMC_SGLD) return (int)hipErrorInvalidValue;
   if (A->chunk_end <= A->chunk_begin) return (int)hipErrorInvalidValue;
   // the template parameter, the launch geometry, the sweep counter and the metric cadence are one per launch
@@ -946,32 +921,9 @@ int sgmcmc_dense_step_multi_args(const sgmcmc_dense_chain* chains_dev, const sgm
         return (int)hipErrorInvalidValue;
   }
   if (A_pending && !(A_pending->flags & SGMCMC_SMALL_FINALIZE)) return (int)hipErrorInvalidValue;
-  const int steps16 = ((mlp.in_features + 15) & ~15) >> 4;
-  if ((steps16 + KSPLIT - 1) / KSPLIT > F1_UNROLL) return (int)hipErrorInvalidValue;
   SGMCMC_FRESH_ERROR_STATE();
-  IdxMulti IM;
-  for (int c = 0; c < n_chains; ++c)
-    for (int b = 0; b < mlp.batch; ++b) IM.idx[c][b] = idx_host[(size_t)c * mlp.batch + b];
-  ArgsMulti AM, AP;
-  for (int c = 0; c < SGMCMC_MAX_CHAINS; ++c) {      // (unused rows repeat chain 0: no uninitialised kernel argument)
-    const int k = c < n_chains ? c : 0;
-    AM.a[c] = A[k];
-    AP.a[c] = A_pending ? A_pending[k] : A[k];
-    AP.a[c].flags &= ~(uint32_t)SGMCMC_DEFER_FINALIZE;
-  }
-  const int slices = (mlp.batch + ROWS - 1) / ROWS;
-  hipStream_t s = (hipStream_t)stream;
-  const unsigned ny = (unsigned)n_chains;
-  SGMCMC_LAUNCH(mlp_f1_multi_kernel, dim3((unsigned)(slices * KSPLIT), ny), dim3(kSplitThreads), 0, s, chains_dev, IM);
-  SGMCMC_LAUNCH(mlp_rest_multi_args_kernel, dim3((unsigned)(slices * KSPLIT + (A_pending ? 1 : 0)), ny),
-                dim3(kSplitThreads), 0, s, chains_dev, AP, A_pending ? 1 : 0);
-  const dim3 grid((unsigned)(A->chunk_end - A->chunk_begin), ny), block(kThreads);
-  switch (A->kind) {
-    case SGMCMC_VERLET: SGMCMC_LAUNCH(step_parts_multi_args_kernel<SGMCMC_VERLET>, grid, block, 0, s, chains_dev, AM); break;
-    case SGMCMC_HMC: SGMCMC_LAUNCH(step_parts_multi_args_kernel<SGMCMC_HMC>, grid, block, 0, s, chains_dev, AM); break;
-    default: SGMCMC_LAUNCH(step_parts_multi_args_kernel<SGMCMC_SGLD>, grid, block, 0, s, chains_dev, AM); break;
-  }
-  return (int)hipGetLastError();
+  return dense_step_multi_launch(chains_dev, chain0_host->mlp, n_chains, A, idx_host, A_pending, true,
+                                 (hipStream_t)stream);
 }
 
 namespace {
@@ -1040,10 +992,7 @@ int sgmcmc_dense_stepper_create(const sgmcmc_layout* L, const sgmcmc_mlp_args* m
   for (int i = 0; i < n_ring && err == hipSuccess; ++i)
     err = hipEventCreateWithFlags(&S->events[i], hipEventDisableTiming);
   if (err != hipSuccess) return (int)err;
-  const int slices = (mlp->batch + SGMCMC_MLP_ROWS - 1) / SGMCMC_MLP_ROWS;
-  sgmcmc_grad_parts G;
-  G.gpart = mlp->gpart; G.loss_part = mlp->loss_part; G.correct_part = mlp->correct_part;
-  G.stride = mlp->gpart_stride; G.num_data = num_data; G.n_slices = slices; G.batch = mlp->batch;
+  const sgmcmc_grad_parts G = grad_parts_of(*mlp, num_data);
   // one eager pass first: loads the code objects and sets the LDS attribute outside capture
   // (writes scratch only: idx = identity, no argument forwarding)
   sgmcmc_mlp_args warm = *mlp;

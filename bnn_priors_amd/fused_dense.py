@@ -64,6 +64,12 @@ def _dense_layers(model):
     return lin
 
 
+def _parse_row(v, n_seg):
+    "a read-back report row: (dict(loss, acc, nonfinite, log_prior, energy), the per-segment state [n_seg][...])"
+    r = dict(loss=float(v[4]), acc=float(v[5]), nonfinite=bool(v[1] != 0.0), log_prior=float(v[2]), energy=float(v[3]))
+    return r, v[8:].reshape(n_seg, -1).copy()
+
+
 class FusedDenseLeapfrog(_ReportSlots):
     @staticmethod
     def supported(potential, optimizer):
@@ -108,6 +114,28 @@ class FusedDenseLeapfrog(_ReportSlots):
         self._init_slots(eng.report.numel())
 
     # ------------------------------------------------------------------ per batch size
+    def _mlp_args(self, *, X, Y, idx, gpart, loss_part, corr_part, batch, grad_scale, split_scratch):
+        """the forward/backward kernels' argument struct for ``batch`` rows of the set at (X, Y) (device addresses), named
+        by the device index array ``idx`` (None: rows 0..batch-1), the partials going to the given tensors"""
+        W1, b1, W2, b2, W3, b3 = self.eng.params
+        o = self.offs
+        return _hip.MlpArgs(
+            X=X, Y=Y, idx=idx, W1=W1.data_ptr(), b1=b1.data_ptr(), W2=W2.data_ptr(), b2=b2.data_ptr(),
+            W3=W3.data_ptr(), b3=b3.data_ptr(), gpart=gpart.data_ptr(), loss_part=loss_part.data_ptr(),
+            correct_part=corr_part.data_ptr(), gpart_stride=self.stride, off_W1=o[0], off_b1=o[1], off_W2=o[2],
+            off_b2=o[3], off_W3=o[4], off_b3=o[5], batch=batch, in_features=W1.shape[1], hidden1=W1.shape[0],
+            hidden2=W2.shape[0], out_features=W3.shape[0],
+            inv_softmax_temp=1.0 / float(self.pot.model.softmax_temp), trace=None,
+            args_src=None, args_dst=None, args_bytes=0, grad_scale=grad_scale, split_scratch=split_scratch)
+
+    def _state_for(self, batch):
+        "the per-batch-size state (buffers, argument structs, graph replicas), set up on first use"
+        st = self._by_batch.get(batch)
+        if st is None:
+            st = self._by_batch[batch] = self._setup(batch)
+            self._static_flags = st["A"].flags & ~_hip.CALC_METRICS
+        return st
+
     def _setup(self, batch):
         eng, dev = self.eng, self.eng.device
         S = -(-batch // _hip.MLP_ROWS)
@@ -119,19 +147,9 @@ class FusedDenseLeapfrog(_ReportSlots):
         st["loss_part"] = torch.zeros(S, device=dev)
         st["corr_part"] = torch.zeros(S, device=dev)
         st["split"] = torch.zeros(self.lib.sgmcmc_mlp_split_scratch_floats(batch), device=dev)
-        W1, b1, W2, b2, W3, b3 = eng.params
-        o = self.offs
-        st["mlp"] = _hip.MlpArgs(
-            X=self.X.data_ptr(), Y=self.Y.data_ptr(), idx=st["dev"].data_ptr() + self.nbytes_args,
-            W1=W1.data_ptr(), b1=b1.data_ptr(), W2=W2.data_ptr(), b2=b2.data_ptr(),
-            W3=W3.data_ptr(), b3=b3.data_ptr(), gpart=st["gpart"].data_ptr(),
-            loss_part=st["loss_part"].data_ptr(), correct_part=st["corr_part"].data_ptr(),
-            gpart_stride=self.stride, off_W1=o[0], off_b1=o[1], off_W2=o[2], off_b2=o[3],
-            off_W3=o[4], off_b3=o[5], batch=batch, in_features=W1.shape[1], hidden1=W1.shape[0],
-            hidden2=W2.shape[0], out_features=W3.shape[0],
-            inv_softmax_temp=1.0 / float(self.pot.model.softmax_temp), trace=None,
-            args_src=None, args_dst=None, args_bytes=0, grad_scale=0.0,
-            split_scratch=st["split"].data_ptr() if self.split else None)
+        st["mlp"] = self._mlp_args(X=self.X.data_ptr(), Y=self.Y.data_ptr(), idx=st["dev"].data_ptr() + self.nbytes_args,
+                                   gpart=st["gpart"], loss_part=st["loss_part"], corr_part=st["corr_part"], batch=batch,
+                                   grad_scale=0.0, split_scratch=st["split"].data_ptr() if self.split else None)
         st["param_ptrs"] = [p.data_ptr() for p in eng.params]
         self._bind_grads()
         eng.refresh(self.opt._preconditioners())
@@ -195,25 +213,15 @@ class FusedDenseLeapfrog(_ReportSlots):
                 acc=torch.zeros(self.stride, dtype=torch.float64, device=dev),
                 gsum=torch.zeros(self.stride, device=dev),
                 stats=torch.zeros(2, dtype=torch.float64, device=dev))
-        W1, b1, W2, b2, W3, b3 = eng.params
-        o = self.offs
         stream = eng.stream()
         self._bind_grads()
         eng.refresh(self.opt._preconditioners())
-        in_f = W1.shape[1]
+        in_f = self.X.shape[1]
         for start in range(0, n_data, self.MEGA):
             mb = min(self.MEGA, n_data - start)
-            A = _hip.MlpArgs(
-                X=self.X.data_ptr() + 4 * start * in_f, Y=self.Y.data_ptr() + 8 * start, idx=None,
-                W1=W1.data_ptr(), b1=b1.data_ptr(), W2=W2.data_ptr(), b2=b2.data_ptr(),
-                W3=W3.data_ptr(), b3=b3.data_ptr(), gpart=ex["gpart"].data_ptr(),
-                loss_part=ex["loss_part"].data_ptr(), correct_part=ex["corr_part"].data_ptr(),
-                gpart_stride=self.stride, off_W1=o[0], off_b1=o[1], off_W2=o[2], off_b2=o[3],
-                off_W3=o[4], off_b3=o[5], batch=mb, in_features=in_f, hidden1=W1.shape[0],
-                hidden2=W2.shape[0], out_features=W3.shape[0],
-                inv_softmax_temp=1.0 / float(self.pot.model.softmax_temp), trace=None,
-                args_src=None, args_dst=None, args_bytes=0, grad_scale=1.0 / self.pot.N,
-                split_scratch=None)
+            A = self._mlp_args(X=self.X.data_ptr() + 4 * start * in_f, Y=self.Y.data_ptr() + 8 * start, idx=None,
+                               gpart=ex["gpart"], loss_part=ex["loss_part"], corr_part=ex["corr_part"], batch=mb,
+                               grad_scale=1.0 / self.pot.N, split_scratch=None)
             _hip.check(lib.sgmcmc_mlp_fwdbwd(ctypes.byref(A), stream), "sgmcmc_mlp_fwdbwd")
             last = start + mb >= n_data
             _hip.check(lib.sgmcmc_accumulate_parts(
@@ -238,15 +246,10 @@ class FusedDenseLeapfrog(_ReportSlots):
         batch = len(idx)
         st = self._by_batch.get(batch)
         eng = self.eng
-        if st is not None:
-            for p, q in zip(eng.params, st["param_ptrs"]):
-                if p.data_ptr() != q:    # parameter storage moved (p.data = ...): re-capture
-                    self.lib.sgmcmc_dense_stepper_destroy(st["handle"])
-                    st = None
-                    break
-        if st is None:
-            st = self._by_batch[batch] = self._setup(batch)
-            self._static_flags = st["A"].flags & ~_hip.CALC_METRICS
+        if st is not None and any(p.data_ptr() != q for p, q in zip(eng.params, st["param_ptrs"])):
+            self.lib.sgmcmc_dense_stepper_destroy(st["handle"])     # parameter storage moved (p.data = ...): re-capture
+            del self._by_batch[batch]
+        st = self._state_for(batch)
         self._bind_grads()
         if eng._seg_dirty or eng._precond_dirty:
             eng.refresh(self.opt._preconditioners())
@@ -278,12 +281,7 @@ class FusedDenseLeapfrog(_ReportSlots):
         buf.copy_(eng.report, non_blocking=True)
         ev.record()
         n_seg = eng.n_seg
-
-        def parse(v):
-            r = dict(loss=float(v[4]), acc=float(v[5]), nonfinite=bool(v[1] != 0.0),
-                     log_prior=float(v[2]), energy=float(v[3]))
-            return r, v[8:].reshape(n_seg, -1).copy()
-        return self._hand_over(PendingRow(self, buf, ev, parse), wait)
+        return self._hand_over(PendingRow(self, buf, ev, lambda v: _parse_row(v, n_seg)), wait)
 
     def _hand_over(self, row, wait):
         """what ``replay`` returns on a metric step, given the row's read-back (``get()`` -> (dict, per-segment state)):
@@ -353,10 +351,7 @@ class MultiChainDense:
         "per-chain pointers, uploaded when any of them changed (first use, roll-back arrays allocated, ...)"
         sig = [batch]
         for s in self.steppers:
-            st = s._by_batch.get(batch)
-            if st is None:
-                st = s._by_batch[batch] = s._setup(batch)
-                s._static_flags = st["A"].flags & ~_hip.CALC_METRICS
+            st = s._state_for(batch)
             s._bind_grads()
             if s.eng._seg_dirty or s.eng._precond_dirty:
                 s.eng.refresh(s.opt._preconditioners())
@@ -489,7 +484,6 @@ class MultiChainDense:
         rows = torch.stack([s.eng.report for s in steppers]).cpu().numpy()      # ... and ONE read-back for all
         out = []
         for s, v in zip(steppers, rows):
-            out.append(dict(loss=float(v[4]), acc=float(v[5]), nonfinite=bool(v[1] != 0.0), log_prior=float(v[2]),
-                            energy=float(v[3])))
-            s.eng._state_host = v[8:].reshape(s.eng.n_seg, -1).copy()
+            r, s.eng._state_host = _parse_row(v, s.eng.n_seg)
+            out.append(r)
         return out

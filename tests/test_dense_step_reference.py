@@ -33,6 +33,9 @@ Largest gradient error observed on an MI355X, as a fraction of the 2e-6 bar (two
   sgmcmc_dense_step_multi_args, a block per chain (Ln .18, M .46)                0.46
 The transition comparison is exact on every route: theta, momentum and square_avg are the oracle's bits.
 """
+import importlib.util
+import json
+import os
 import types
 
 import numpy as np
@@ -43,6 +46,11 @@ import dense_step_helpers as H
 
 pytestmark = pytest.mark.gpu
 DEV = H.DEV
+
+_spec = importlib.util.spec_from_file_location(
+    "make_dense_step_bits", os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "make_dense_step_bits.py"))
+bits = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(bits)
 
 
 def _prepare(case, c):
@@ -254,3 +262,50 @@ def test_ladder_of_three_chains_each_with_its_own_scalars():
     "M: T = 1 / 0.1 / 0, learning rate, momentum and the data-set size differ per chain: sgmcmc_dense_step_multi_args"
     chains = _run_multi("M", "sgmcmc_dense_step_multi_args")
     assert len({ch.N for ch in chains}) == 3
+
+
+# ------------------------------------------------------------------ the bits themselves
+@pytest.fixture(scope="module")
+def recorded_bits():
+    with open(bits.PATH) as fh:
+        return json.load(fh)
+
+
+@pytest.mark.parametrize("name", list(H.CASES))
+def test_every_route_reproduces_the_recorded_bits(name, recorded_bits):
+    """sha256 of gpart / loss_part / corr_part, g_flat and every tensor of theta, momentum and square_avg after every step
+    of every chain, against tests/golden/dense_step_bits.json -- recorded (tests/golden/make_dense_step_bits.py) with the
+    library as it was before the phases of csrc/mlp_hip.inc were written once for both kernel families.  The library is
+    built with -ffp-contract=off: the same operations in the same order are the same bits."""
+    want, got = recorded_bits["cases"][name], bits.digests(name)
+    assert len(got) == len(want) == len(H.case_of(name)["n"])
+    for c, (gc, wc) in enumerate(zip(got, want)):
+        assert len(gc) == len(wc) == H.case_of(name)["steps"]
+        for t, (gs, ws) in enumerate(zip(gc, wc)):
+            assert sorted(gs) == sorted(ws)
+            for array in gs:
+                assert gs[array] == ws[array], (
+                    f"case {name} chain {c} step {t}: {array} differs from the recording "
+                    f"(recorded under {recorded_bits['versions']}, running {bits.versions()})")
+
+
+def _same_trajectory(a, b, what):
+    "g_flat, theta, momentum and square_avg of two drives of one problem, after every step"
+    a, b = list(a), list(b)
+    assert len(a) == len(b) > 0
+    for (c, t, xa), (_, _, xb) in zip(a, b):
+        xb = dict(xb)
+        for array, ta in xa:
+            if array not in ("gpart", "loss_part", "corr_part"):      # (per-slice partials: a route's own scratch)
+                assert torch.equal(ta, xb[array]), f"{what}: chain {c} step {t}: {array}"
+
+
+def test_routes_agree_bit_for_bit():
+    """The two-launch split, the inline one-launch kernels and the graph replicas run the same phase functions, so
+    wherever a K quarter has at most F1_UNROLL = 13 steps they perform the same operations in the same order: B against G
+    (``split`` off), B against H (the graph route, with B's metric steps, three steps), and D -- the split at its limit
+    -- against D with ``split`` off."""
+    B = list(bits.tensors_per_step("B"))
+    _same_trajectory(B, bits.tensors_per_step("G"), "B vs G")
+    _same_trajectory(B, bits.tensors_per_step("H", metric=H.case_of("B")["metric"], steps=H.case_of("B")["steps"]), "B vs H")
+    _same_trajectory(bits.tensors_per_step("D"), bits.tensors_per_step("D", split=False), "D vs D without the split")
