@@ -1712,3 +1712,5 @@ int sgmcmc_debug_normals(float* out, int64_t start, int64_t n, uint64_t seed, ui
 #include "augment_hip.inc"
 // calibration / OOD-detection metrics of a posterior ensemble (evaluation side, fp64)
 #include "calib_hip.inc"
+// between-chain diagnostics of stored draws: split-R-hat and effective sample size (fp64)
+#include "diag_hip.inc"

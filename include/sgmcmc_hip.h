@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGMCMC_ABI_VERSION 12
+#define SGMCMC_ABI_VERSION 13
 #define SGMCMC_CHUNK 4096 /* default elements per arena chunk = 256 threads x 4 items x 4 elements */
 #define SGMCMC_CHUNK_SMALL 1024 /* small models: one item per thread, 4x more workgroups */
 #define SGMCMC_NSUMS 6
@@ -907,6 +907,44 @@ int sgmcmc_calibration_error(const double* keys, int64_t elem_stride, int64_t co
  * 2 area = sum dFP (TP_prev + TP) in integers, out[1] = sum (R_k - R_{k-1}) P_k over the thresholds in descending
  * order, out[2] = 1 if a score is NaN (out[0], out[1] NaN then), else 0.  0 < n_pos < n. */
 int sgmcmc_rank_metrics(const double* scores, const int32_t* perm, int n, int n_pos, double* out, void* stream);
+
+/* ---- Between-chain diagnostics of stored draws: split-R-hat and effective sample size (fp64, deterministic) ----------
+ * The reference has no such function; this is the definition (Gelman et al., BDA3 section 11.4-11.5; Geyer 1992;
+ * Vehtari et al. 2021 without the rank normalisation).  x[m][s][q]: `chains` x `draws` x `quantities` values, fp32
+ * (is_f64 = 0) or fp64, element (m, s, q) at x[m * chain_stride + s * draw_stride + q]; fp32 is widened on load and all
+ * arithmetic is fp64.
+ *  1. split != 0: n = draws / 2, every chain gives the sequences of its draws [0, n) and [draws - n, draws) (an odd
+ *     count loses its middle draw, which is never read), J = 2 chains; split == 0: n = draws, J = chains.
+ *  2. per sequence j and quantity: the mean mu_j, c_s = x_s - mu_j (two passes) and the biased autocovariance
+ *     a_j[t] = (1/n) sum_{s=0}^{n-1-t} c_s c_{s+t}, t = 0 .. n-1.
+ *  3. W = mean_j a_j[0] n/(n-1); B/n = var_j(mu_j) with ddof = 1 (0 if J = 1); var+ = W (n-1)/n + B/n.
+ *  4. rhat = sqrt(var+ / W).
+ *  5. rho_0 = 1, rho_t = 1 - (W - mean_j a_j[t]) / var+ for t >= 1.
+ *  6. P_k = rho_{2k} + rho_{2k+1}, k = 0 .. n/2 - 1; K = the smallest k >= 1 with P_k <= 0, or n/2 if there is none;
+ *     P'_0 = P_0, P'_k = min(P'_{k-1}, P_k).
+ *  7. tau = -1 + 2 sum_{k<K} P'_k, raised to at least 1 / log10(J n); ess = J n / tau.
+ *  8. a quantity with a non-finite draw in one of its sequences, or with W = 0, gives NaN for rhat and ess (and
+ *     pairs = 0); nothing else is special-cased.
+ * Every sum runs in an order fixed by (chains, draws, split): the mean as SGMCMC_DIAG_MEAN_WAYS interleaved partial sums
+ * added in order, a_j[t] over ascending s, sums over j in ascending j (the means by Welford's update).  A quantity's
+ * result does not depend on the other quantities of the call, and sgmcmc_chain_rhat equals the rhat of sgmcmc_chain_ess
+ * bit for bit.  Limits: 4 <= n <= SGMCMC_DIAG_MAX_SEQ, J <= SGMCMC_DIAG_MAX_CHAINS, strides >= 0; anything else returns
+ * hipErrorInvalidValue and launches nothing. */
+#define SGMCMC_DIAG_MAX_SEQ 512    /* n: a [n][SGMCMC_DIAG_TILE] fp64 tile of centred draws is staged in LDS (128 KiB) */
+#define SGMCMC_DIAG_MAX_CHAINS 64  /* J */
+#define SGMCMC_DIAG_LAG_BLOCK 32   /* lags per pass of sgmcmc_chain_ess over the sequences */
+#define SGMCMC_DIAG_TILE 32        /* quantities per workgroup of sgmcmc_chain_ess */
+#define SGMCMC_DIAG_MEAN_WAYS 8    /* partial sums of every mean */
+
+/* rhat [quantities]: steps 1-4 and 8.  One launch, one thread per quantity, the data read twice. */
+int sgmcmc_chain_rhat(const void* x, int is_f64, int64_t chain_stride, int64_t draw_stride, int chains, int draws,
+                      int64_t quantities, int split, double* rhat, void* stream);
+/* ess [quantities]: steps 1-8; rhat [quantities] (may be NULL); pairs [quantities] (int32, may be NULL) receives K.
+ * One launch: a workgroup per SGMCMC_DIAG_TILE quantities walks the lags in blocks of SGMCMC_DIAG_LAG_BLOCK, re-reading
+ * the sequences once per block, and stops after the block in which the last quantity of its tile found its K (lags
+ * above 2K + 1 enter no result): one pass for well-mixed chains, n / SGMCMC_DIAG_LAG_BLOCK passes at worst. */
+int sgmcmc_chain_ess(const void* x, int is_f64, int64_t chain_stride, int64_t draw_stride, int chains, int draws,
+                     int64_t quantities, int split, double* ess, double* rhat, int32_t* pairs, void* stream);
 
 /* Test hook: out[i] = spec normal (fp32) of noise index start+i. */
 int sgmcmc_debug_normals(float* out, int64_t start, int64_t n, uint64_t seed, uint32_t stream,
