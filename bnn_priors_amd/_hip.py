@@ -24,7 +24,7 @@ INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 SOURCES = [os.path.join(_HERE, "csrc", "sgmcmc_hip.hip")]
 SOURCE = SOURCES[0]
 
-ABI_VERSION = 13
+ABI_VERSION = 14
 CHUNK = 4096
 CHUNK_SMALL = 1024
 NSUMS = 6
@@ -178,6 +178,7 @@ class DenseChain(ctypes.Structure):
 
 MAX_CHAINS, MLP_BATCH_MULTI = 8, 128
 DIAG_MAX_SEQ, DIAG_MAX_CHAINS, DIAG_LAG_BLOCK, DIAG_TILE = 512, 64, 32, 32
+RANK_OWN, RANK_MAX_PROBS = 16, 3
 
 EXPORTS = {
     "sgmcmc_abi_version": (ctypes.c_int, []),
@@ -345,6 +346,16 @@ EXPORTS = {
                                          ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
     "sgmcmc_chain_ess": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                                         ctypes.c_int, ctypes.c_int64, ctypes.c_int] + [ctypes.c_void_p] * 4),
+    "sgmcmc_chain_rank_scores": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
+                                                ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
+                                                ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.c_int]
+                                 + [ctypes.c_void_p] * 3),
+    "sgmcmc_chain_quantiles": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                              ctypes.POINTER(ctypes.c_double), ctypes.c_int, ctypes.c_int64,
+                                              ctypes.c_void_p, ctypes.c_void_p]),
+    "sgmcmc_chain_tail_indicators": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
+                                                    ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int]
+                                     + [ctypes.c_void_p] * 5),
     "sgmcmc_debug_normals": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                             ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64,
                                             ctypes.c_uint32, ctypes.c_void_p]),

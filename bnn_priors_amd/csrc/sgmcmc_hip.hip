@@ -1714,3 +1714,5 @@ int sgmcmc_debug_normals(float* out, int64_t start, int64_t n, uint64_t seed, ui
 #include "calib_hip.inc"
 // between-chain diagnostics of stored draws: split-R-hat and effective sample size (fp64)
 #include "diag_hip.inc"
+// ... and their rank-normalised form: normal scores of the average ranks, tail quantiles and indicators (fp64)
+#include "rank_hip.inc"

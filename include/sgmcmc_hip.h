@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGMCMC_ABI_VERSION 13
+#define SGMCMC_ABI_VERSION 14
 #define SGMCMC_CHUNK 4096 /* default elements per arena chunk = 256 threads x 4 items x 4 elements */
 #define SGMCMC_CHUNK_SMALL 1024 /* small models: one item per thread, 4x more workgroups */
 #define SGMCMC_NSUMS 6
@@ -945,6 +945,59 @@ int sgmcmc_chain_rhat(const void* x, int is_f64, int64_t chain_stride, int64_t d
  * above 2K + 1 enter no result): one pass for well-mixed chains, n / SGMCMC_DIAG_LAG_BLOCK passes at worst. */
 int sgmcmc_chain_ess(const void* x, int is_f64, int64_t chain_stride, int64_t draw_stride, int chains, int draws,
                      int64_t quantities, int split, double* ess, double* rhat, int32_t* pairs, void* stream);
+
+/* ---- Rank-normalised R-hat, bulk ESS and tail ESS (Vehtari, Gelman, Simpson, Carpenter, Buerkner 2021) ---------------
+ * The moment-based definition above assumes a finite mean and variance; under heavy-tailed priors (cauchy, student-t
+ * with few degrees of freedom, horseshoe) it says little.  This is the definition of the rank-normalised one.  x, split,
+ * n, J and the sequences are as above; N = J n.  For one quantity v_1 .. v_N are the draws that enter the sequences, in
+ * sequence order (sequence 0 first; with split and an odd count a chain's middle draw enters nothing); fp32 is widened
+ * on load; -0.0 counts as, and is written as, +0.0.  Rhat(.), Ess(.) and K(.) are steps 2-8 above applied to J
+ * sequences of n values without a further split.
+ *   average rank   r_i = #{j : v_j < v_i} + (#{j : v_j = v_i} + 1) / 2 over all N draws (the second count includes i):
+ *                  integer counts, so ranks are exact
+ *   normal score   z(v)_i = ndtri((r_i - 3/8) / (N + 1/4)): numerator and denominator are exact in fp64, the quotient is
+ *                  one correctly rounded division; ndtri is the inverse of the standard normal distribution function
+ *                  (Cephes' rational approximations)
+ *   quantile       type 7 (numpy's "linear"): pos = (N - 1) p, lo = floor(pos), hi = min(lo + 1, N - 1),
+ *                  q_p(v) = v_(lo) + (v_(hi) - v_(lo)) (pos - lo), v_(k) the k-th smallest counted from 0; every
+ *                  operation is rounded once (nothing is contracted into an fma), and in numpy's order: with
+ *                  d = v_(hi) - v_(lo) and t = pos - lo, v_(lo) + d t if t < 0.5, else v_(hi) - d (1 - t) -- the same
+ *                  number, interpolated from the nearer neighbour, so that q_p equals np.quantile(method="linear")
+ *                  bit for bit; the median is q_0.5
+ *   results        rhat     = max(Rhat(z(v)), Rhat(z(|v - q_0.5(v)|)))        (the subtraction rounded once)
+ *                  ess_bulk = Ess(z(v))
+ *                  ess_tail = min(Ess(1[v <= q_plo(v)]), Ess(1[v <= q_phi(v)])), (plo, phi) = (0.05, 0.95) by default
+ *   NaN rule       a quantity with a non-finite draw gives NaN in all three; otherwise rhat is NaN if either part is
+ *                  (a constant column), ess_tail is NaN if either indicator's Ess is (a constant indicator: enough
+ *                  draws tie at an extreme).
+ * For even N the two middle draws have mathematically equal folded values, and whether they tie in floating point
+ * decides two ranks: hence the singly rounded median and subtraction (frac = 0.5: the product is exact).
+ * The three entries below produce the [J][n][Q] arrays; sgmcmc_chain_rhat / sgmcmc_chain_ess (chains = J, draws = n,
+ * split = 0) turn them into the parts, and the caller combines the parts (bnn_priors_amd/diagnostics.py rank_rhat_ess).
+ * No atomics; ranks are counted, so no schedule can change a bit; a quantity's result depends on its own column only.
+ * The caller provides every buffer; nothing is allocated and nothing synchronises.  An argument set that
+ * sgmcmc_chain_ess refuses, a NULL required pointer or a p outside (0, 1) returns hipErrorInvalidValue and launches
+ * nothing. */
+#define SGMCMC_RANK_OWN 16         /* draws of its quantity that a thread of the score kernel ranks */
+#define SGMCMC_RANK_MAX_PROBS 3    /* quantile probabilities per call */
+
+/* z [J][n][quantities] (fp64, contiguous): the normal scores of x, or with centre [quantities] != NULL of
+ * |x - centre|.  nprobs > 0: probs [nprobs] (HOST memory, each in (0, 1), at most SGMCMC_RANK_MAX_PROBS) and ostat
+ * [2 nprobs][quantities] receives the order statistics v_(lo), v_(hi) of probs[i] in rows 2 i, 2 i + 1 (of the folded
+ * values if centre is given); nprobs = 0: probs and ostat may be NULL.  A quantity with a non-finite (folded) draw gets
+ * NaN in all of z and ostat.  One launch: lane = quantity, a thread keeps SGMCMC_RANK_OWN draws in registers and
+ * streams the N draws of its column, counting less and equal; N^2 quantities comparisons. */
+int sgmcmc_chain_rank_scores(const void* x, int is_f64, int64_t chain_stride, int64_t draw_stride, int chains,
+                             int draws, int64_t quantities, int split, const double* centre, const double* probs,
+                             int nprobs, double* z, double* ostat, void* stream);
+/* out [nprobs][quantities]: q_p of probs[i] (HOST memory) from ostat as sgmcmc_chain_rank_scores wrote it for the same
+ * (chains, draws, split, probs). */
+int sgmcmc_chain_quantiles(const double* ostat, int chains, int draws, int split, const double* probs, int nprobs,
+                           int64_t quantities, double* out, void* stream);
+/* lower, upper [J][n][quantities] (fp32, contiguous; 0 and 1 are exact): 1[x <= q_lower[q]] and 1[x <= q_upper[q]]. */
+int sgmcmc_chain_tail_indicators(const void* x, int is_f64, int64_t chain_stride, int64_t draw_stride, int chains,
+                                 int draws, int64_t quantities, int split, const double* q_lower,
+                                 const double* q_upper, float* lower, float* upper, void* stream);
 
 /* Test hook: out[i] = spec normal (fp32) of noise index start+i. */
 int sgmcmc_debug_normals(float* out, int64_t start, int64_t n, uint64_t seed, uint32_t stream,

@@ -1,5 +1,7 @@
 """Time of the two chain-diagnostic entries (``sgmcmc_chain_rhat``, ``sgmcmc_chain_ess``; bnn_priors_amd/diagnostics.py)
-at the shapes of a stored run:
+and of the rank-normalised path built on them (``diagnostics.rank_rhat_ess``: ``sgmcmc_chain_rank_scores`` twice,
+``sgmcmc_chain_quantiles``, ``sgmcmc_chain_tail_indicators``, the R-hat entry once and the ESS entry three times per
+chunk of quantities) at the shapes of a stored run:
 
 * weights    -- 8 chains x 300 draws x 272,474 fp32 quantities (googleresnet's weights), iid normal draws;
 * table      -- 4 chains x 100 draws x 100,000 fp64 quantities (a CIFAR-10 test table of probabilities), iid normal;
@@ -9,9 +11,11 @@ at the shapes of a stored run:
 Per entry: device-event time per call (warm-up, then ``--reps`` calls between two events), and the bytes of ONE pass
 over the data divided by that time (the R-hat entry reads the data twice and the ESS entry once per lag block, so this
 is a rate of diagnosed data, not a memory bandwidth).  For scale: the same definition in numpy on the host
-(tests/chain_diag_reference.py) on a 4,096-quantity slice, scaled to the full width.
+(tests/chain_diag_reference.py; tests/rank_diag_reference.py for the ``rank`` rows) on a 4,096-quantity slice, scaled
+to the full width.  The ``rank`` rows (the two iid shapes) are bound by the N^2 comparisons per quantity of the ranking,
+not by memory, and take ``--rank-reps`` calls per figure.
 
-    python tools/diag_rate.py [--reps 10] [--out profiles/diag_rate.txt]
+    python tools/diag_rate.py [--reps 10] [--rank-reps 2] [--out profiles/diag_rate.txt]
 """
 import argparse
 import os
@@ -25,6 +29,7 @@ import torch  # noqa: E402
 
 from bnn_priors_amd import _hip, diagnostics  # noqa: E402
 from chain_diag_reference import chain_diag_reference  # noqa: E402
+from rank_diag_reference import rank_diag_reference  # noqa: E402
 
 HOST_SLICE = 4096
 
@@ -55,12 +60,13 @@ def _event_ms(fn, reps, warmup=2):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--rank-reps", type=int, default=2)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "diag_rate.txt"))
     a = ap.parse_args()
     assert torch.cuda.is_available(), "diag_rate.py measures on the GPU"
     dev = "cuda:0"
     lines = [f"chain diagnostics, {torch.cuda.get_device_name(0)}, library {_hip.library_sha()} (sources "
-             f"{_hip.source_sha()}), {a.reps} calls per figure, split chains",
+             f"{_hip.source_sha()}), {a.reps} calls per figure ({a.rank_reps} for rank), split chains",
              f"{'shape':28s} {'entry':6s} {'ms/call':>9s} {'GB/s of one pass':>17s} {'lag blocks (max)':>17s} "
              f"{'host numpy s (scaled)':>22s}"]
     for name, M, S, Q, dtype, phi in (("weights 8x300x272474 fp32", 8, 300, 272474, torch.float32, 0.0),
@@ -77,6 +83,13 @@ def main():
             ms = _event_ms(fn, a.reps)
             lines.append(f"{name:28s} {entry:6s} {ms:9.3f} {nbytes / ms * 1e-6:17.1f} "
                          f"{(blocks if entry == 'ess' else 0):17d} {host_s:22.1f}")
+            print(lines[-1], flush=True)
+        if not phi:
+            t0 = time.perf_counter()
+            rank_diag_reference(x[..., :HOST_SLICE].cpu().numpy())
+            host_s = (time.perf_counter() - t0) * Q / HOST_SLICE
+            ms = _event_ms(lambda: diagnostics.rank_rhat_ess(x), a.rank_reps, warmup=1)
+            lines.append(f"{name:28s} {'rank':6s} {ms:9.3f} {nbytes / ms * 1e-6:17.1f} {0:17d} {host_s:22.1f}")
             print(lines[-1], flush=True)
         del x
     text = "\n".join(lines) + "\n"
