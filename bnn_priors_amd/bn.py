@@ -154,16 +154,15 @@ def train_fwd(lib, x, residual, weight, bias, running_mean, running_var, momentu
 
 def sum_groups(dgb, weight, bias):
     """(dgamma, dbeta) of parameters shared by the G groups from dgb [G, 2, C]: views of ONE [2, C] tensor that the
-    pass's deferred slab reduction fills (conv._pending: G slabs of 2 C numbers, fixed order), or an immediate sum"""
+    pass's deferred slab reduction fills (conv.slabs_for: G slabs of 2 C numbers, fixed order), or an immediate sum"""
     G, _, c = dgb.shape
     if G == 1:
         return dgb[0, 0], dgb[0, 1]
     out = torch.empty((2, c), dtype=torch.float32, device=dgb.device)
-    if _conv._may_defer(weight, bias):
-        torch.autograd.Variable._execution_engine.queue_callback(_conv._flush_pending)
-        _conv._pending.append((dgb, out, G, 1))
-        return out[0], out[1]
-    torch.sum(dgb, dim=0, out=out)
+    S = _conv.slabs_for(weight, bias)
+    if not S.defer:         # (ATen's summation order: what this path has always returned)
+        torch.sum(dgb, dim=0, out=out)
+    out = S.hand(dgb, out, 1, G)
     return out[0], out[1]
 
 

@@ -129,6 +129,59 @@ def frags(w):
 # Everywhere else -- user code calling these operators directly -- the reduction is launched immediately.
 _defer = {"active": False, "uses": {}, "weights": {}}
 
+# Weight-gradient slabs whose reduction waits for the end of the running backward pass, where ONE launch
+# sums all of them (autograd's final callback): entries (slabs, out, n_slabs, taps) of ``_fill_jobs``.
+_pending = []
+
+
+class _Slabs:
+    """The hand-over of ONE backward call's partial slabs -- the only place that queues the final callback and
+    appends to ``_pending``.  Protocol, for a ``backward`` that has just computed slabs ``part`` ([n_slabs][out.numel()])
+    of a gradient ``out`` it allocated itself:
+
+        S = slabs_for(w [, bias ...])          # decides once (``_may_defer``); queues ``_flush_pending`` if it defers
+        launch(..., S.ref, ...)                # byref(slab count) or NULL: NULL makes the entry point reduce by itself
+        return S.hand(part, out, taps)         # ``out``, or -- deferring -- an alias of it and one pending job
+
+    ``S.finish`` is ``hand`` for launches that never reduce their own slabs (they always get ``byref(S.count)``).  Who may
+    call: ``backward`` of an autograd function whose forward announced the parameters with ``_note_use``, on a gradient
+    nobody has read; what is returned goes to autograd as that parameter's gradient and nowhere else.  The alias is
+    the point: AccumulateGrad only adopts a gradient nobody else references (``_pending`` holds ``out``), and it must
+    adopt -- not copy -- this one, whose memory is filled at the end of the pass."""
+    __slots__ = ("defer", "count")
+
+    def __init__(self, defer):
+        self.defer, self.count = defer, ctypes.c_int(0)
+        if defer:           # every deferring call queues it; the first one to run does the work
+            torch.autograd.Variable._execution_engine.queue_callback(_flush_pending)
+
+    @property
+    def ref(self):
+        return ctypes.byref(self.count) if self.defer else None
+
+    def hand(self, part, out, taps, n_slabs=None):
+        "``n_slabs`` None: what the launch left in ``count``; slabs of ``taps`` > 1 are tap-major (sgmcmc_reduce_job.taps)"
+        if not self.defer:
+            return out
+        _pending.append((part, out, self.count.value if n_slabs is None else n_slabs, taps))
+        return out.view(out.shape)
+
+    def finish(self, part, out, taps, n_slabs=None):
+        if self.defer:
+            return self.hand(part, out, taps, n_slabs)
+        _reduce_now([(part, out, self.count.value if n_slabs is None else n_slabs, taps)])
+        return out
+
+
+def slabs_for(*params, when=True):
+    "the hand-over of a backward call that produces the gradients of ``params``: defers only if ALL of them qualify"
+    return _Slabs(bool(when) and _may_defer(*params))
+
+
+def reduce_or_defer(part, out, n_slabs, taps, *params):
+    "out <- the sum of ``part``'s slabs, now (one launch) or with the pass's other slabs; -> what autograd gets for ``out``"
+    return slabs_for(*params).finish(part, out, taps, n_slabs)
+
 # ---- zeroed integer slots for grid-wide sums (csrc/conv_hip.inc namespace fx) ---------------------------------------
 # A launch that leaves per-channel sums in fx slots ADDS to them, so they have to be zero beforehand.  Inside a
 # ``deferring`` scope the slots of a pass are slices of ONE arena zeroed by one launch: a fresh arena per captured graph
@@ -212,8 +265,13 @@ def _note_use(*weights):
 
 
 def _may_defer(*weights):
-    return (_defer["active"] and not torch.is_grad_enabled()
-            and all(w.is_leaf and w.grad is None and _defer["uses"].get(id(w), 0) == 1 for w in weights))
+    if not _defer["active"] or torch.is_grad_enabled():
+        return False
+    uses = _defer["uses"]
+    for w in weights:      # (a plain loop: this runs in every operator's backward)
+        if not (w.is_leaf and w.grad is None and uses.get(id(w), 0) == 1):
+            return False
+    return True
 
 
 def supported(x, w, bias, stride, padding, dilation, groups):
@@ -288,11 +346,22 @@ def split_backward(lib, x, w, dy, dx, E, scratch, slabs):
         _hip.check(err, "sgmcmc_conv3x3_bwd_part(data)")
 
 
-def frag_backward(lib, x, w, dy, defer, add=None, sums_for=None):
+def sums_epilogue(E, y_bn, out_bn, saved_bn, partial, group_imgs):
+    """the SUMS half of a ConvBwdEpilogue: the launch also leaves, in ``partial``, the partial sums of the backward of the
+    BatchNorm + ReLU (y_bn -> out_bn, saved statistics saved_bn) whose incoming gradient its dx is"""
+    E.s_y, E.s_out, E.s_mean, E.s_invstd = y_bn.data_ptr(), out_bn.data_ptr(), saved_bn[0].data_ptr(), saved_bn[1].data_ptr()
+    E.s_partial = partial.data_ptr()
+    E.group_imgs = group_imgs
+    E.mask_dx = int(_bnlink.PREMASK)         # dx leaves as dx * [out_bn > 0]: what its consumers form from it
+    return E
+
+
+def frag_backward(lib, x, w, dy, defer, add=None, sums_for=None, G=None):
     """Both gradients of y = conv3x3(x, w) by the persistent launch (sgmcmc_conv3x3_frag_bwd).  ``add`` = (e_dout,
     e_out): dx += e_dout * [e_out > 0]; ``sums_for`` = (y_bn, out_bn, saved_bn): also the partial sums of the BatchNorm
-    backward whose incoming gradient dx is.  -> (dx, dw, partial or None, n_partials); with ``defer`` dw is an alias
-    whose memory the pass's final reduction fills (one job per 16-output-channel tile)."""
+    backward whose incoming gradient dx is (``G`` minibatches in the launch; None: bn.groups()).  -> (dx, dw, partial or
+    None, n_partials); with ``defer`` (inside a backward pass only) dw is an alias whose memory the pass's final reduction
+    fills (one job per 16-output-channel tile)."""
     n, c, hw = x.shape[0], x.shape[1], x.shape[2]
     scratch = torch.empty(lib.sgmcmc_conv3x3_frag_scratch_floats(n, c, hw), dtype=torch.float32, device=x.device)
     dx = torch.empty_like(x)
@@ -302,23 +371,17 @@ def frag_backward(lib, x, w, dy, defer, add=None, sums_for=None):
         E.e_dout, E.e_out = add[0].data_ptr(), 0 if add[1] is None else add[1].data_ptr()
     partial, n_part = None, lib.sgmcmc_conv3x3_frag_stat_slices(n, c, hw)
     if sums_for is not None:
-        y_bn, out_bn, saved_bn = sums_for
         partial = torch.empty((c, n_part, 2), dtype=torch.float64, device=x.device)
-        E.s_y, E.s_out, E.s_mean, E.s_invstd = (y_bn.data_ptr(), out_bn.data_ptr(), saved_bn[0].data_ptr(),
-                                                saved_bn[1].data_ptr())
-        E.s_partial = partial.data_ptr()
-        E.group_imgs = _group_imgs(n)
-        E.mask_dx = int(_bnlink.PREMASK)         # dx leaves as dx * [out_bn > 0]: what its consumers form from it
-    slabs = ctypes.c_int(0)
+        sums_epilogue(E, *sums_for, partial, _group_imgs(n, G))
+    S = _Slabs(defer)
     err = lib.sgmcmc_conv3x3_frag_bwd(x.data_ptr(), frags(w)[1].data_ptr(), dy.data_ptr(), dx.data_ptr(), ctypes.byref(E),
-                                      0 if defer else dw.data_ptr(), scratch.data_ptr(), n, c, hw,
-                                      ctypes.byref(slabs) if defer else None, _stream())
+                                      0 if defer else dw.data_ptr(), scratch.data_ptr(), n, c, hw, S.ref, _stream())
     if err:
         _hip.check(err, "sgmcmc_conv3x3_frag_bwd")
     if defer:
-        P, slab = slabs.value, 144 * c          # [tile][P][9][16][C]: one reduction job per output-channel tile
+        P, slab = S.count.value, 144 * c          # [tile][P][9][16][C]: one reduction job per output-channel tile
         for t in range(c // 16):
-            _pending.append((scratch[t * P * slab:(t + 1) * P * slab], dw[16 * t:16 * (t + 1)], P, 9))
+            S.hand(scratch[t * P * slab:(t + 1) * P * slab], dw[16 * t:16 * (t + 1)], 9)
         return dx, dw.view(dw.shape), partial, n_part
     return dx, dw, partial, n_part
 
@@ -328,72 +391,61 @@ def frag_backward(lib, x, w, dy, defer, add=None, sums_for=None):
 WRW_GROUP_MULT = True
 
 
-def _group_imgs(n):
+def _group_imgs(n, G=None):
     "images per group for a launch that looks a BatchNorm's saved statistics up by image (bn.grouped); 0: one batch"
-    from . import bn as _bn
-    G = _bn.groups()
+    if G is None:
+        from . import bn as _bn
+        G = _bn.groups()
     if G > 1 and SIDE_STREAM:
         raise RuntimeError("bn.grouped(G > 1) does not run with the side-stream alternative")
     return n // G if G > 1 else 0
 
 
-def _both_grads(x, w, dy, defer, sums_for=None):
-    "``sums_for`` = (y_bn, out_bn, saved_bn) of the BatchNorm + ReLU that produced x: its backward sums ride along"
-    lib = _hip.lib()
+def trunk_backward(lib, x, w, dy, s, add=None, sums_for=None, G=1):
+    """Both gradients of y = conv3x3(x, w) given dy -- THE backward driver of the trunk's 3x3 convolutions, for the
+    layer-by-layer operator (``_both_grads``) and the fused residual block (resblock.py) alike.  ``add`` = (e_dout,
+    e_out): dx += e_dout * [e_out > 0] (e_out None: e_dout is masked already); ``sums_for`` = (y_bn, out_bn, saved_bn):
+    also the partial sums of the BatchNorm backward whose incoming gradient dx is, and (bnlink.PREMASK) dx is stored
+    as dx * [out_bn > 0]; ``G``: minibatches in the launch (bn.grouped) -> (dx, dw, partial or None, n_partials).
+
+    Three routes, each written here once: the persistent launch (``frag_backward``), the side-stream alternative
+    (``split_backward``; refuses G > 1) and the merged launch, which takes the pass's pending slab reductions along
+    (``take_riders``).  The merged launch never reduces its own slabs: ``_Slabs.finish`` does, now or at the end of the
+    pass.  ``wrw_mult`` is always set to ``WRW_GROUP_MULT and G`` (the C side ignores it without sums); ``group_imgs``
+    comes from ``G``, which the layered operator takes from ``bn.groups()`` and the block from its forward."""
     n, c, hw = x.shape[0], x.shape[1], x.shape[2]
-    if persistent_bwd(c, hw) and not (defer and SIDE_STREAM):
-        dx, dw, partial, n_part = frag_backward(lib, x, w, dy, defer, sums_for=sums_for)
-        if partial is not None:
-            _bnlink.tag_gradient(dx, partial, n_part, _bnlink.PREMASK)
-        return dx, dw
-    scratch = torch.empty(lib.sgmcmc_conv3x3_wrw_scratch_floats(n, c, hw), dtype=torch.float32, device=x.device)
+    defer = _may_defer(w)
+    if persistent_bwd(c, hw) and not (SIDE_STREAM and defer):
+        return frag_backward(lib, x, w, dy, defer, add=add, sums_for=sums_for, G=G)
+    part = torch.empty(lib.sgmcmc_conv3x3_wrw_scratch_floats(n, c, hw), dtype=torch.float32, device=x.device)
     dx = torch.empty_like(x)
-    dw = torch.empty((c, c, 3, 3), dtype=torch.float32, device=x.device)
-    slabs = ctypes.c_int(0)
-    if defer and SIDE_STREAM:
-        partial, E = None, None
-        if sums_for is not None:
-            y_bn, out_bn, saved_bn = sums_for
-            n_part = lib.sgmcmc_conv3x3_stat_slices(n, c, hw)
-            partial = torch.empty((c, n_part, 2), dtype=torch.float64, device=x.device)
-            E = _hip.ConvBwdEpilogue(s_y=y_bn.data_ptr(), s_out=out_bn.data_ptr(), s_mean=saved_bn[0].data_ptr(),
-                                     s_invstd=saved_bn[1].data_ptr(), s_partial=partial.data_ptr(),
-                                     mask_dx=int(_bnlink.PREMASK))
-        split_backward(lib, x, w, dy, dx, E, scratch, slabs)
-        if partial is not None:
-            _bnlink.tag_gradient(dx, partial, n_part, _bnlink.PREMASK)
-        _pending.append((scratch, dw, slabs.value, 9))
-        return dx, dw.view(dw.shape)
-    riders = take_riders(c, hw)
-    if sums_for is None and riders is not None:       # (an empty epilogue: the launch of sgmcmc_conv3x3_bwd)
-        err = bwd_ex(lib, x, w, dy, dx, _hip.ConvBwdEpilogue(), dw, scratch, slabs if defer else None, _stream(), riders)
-    elif sums_for is None:
-        err = lib.sgmcmc_conv3x3_bwd(x.data_ptr(), w.data_ptr(), dy.data_ptr(), dx.data_ptr(), dw.data_ptr(),
-                                     scratch.data_ptr(), n, c, hw, ctypes.byref(slabs) if defer else None, _stream())
+    E = _hip.ConvBwdEpilogue()
+    E.wrw_mult = WRW_GROUP_MULT and G       # (several minibatches: the slab count of one)
+    if add is not None:
+        E.e_dout, E.e_out = add[0].data_ptr(), 0 if add[1] is None else add[1].data_ptr()
+    partial, n_partials = None, lib.sgmcmc_conv3x3_stat_slices(n, c, hw)
+    if sums_for is not None:
+        partial = torch.empty((c, n_partials, 2), dtype=torch.float64, device=x.device)
+        sums_epilogue(E, *sums_for, partial, _group_imgs(n, G))
+    S = _Slabs(defer)
+    if SIDE_STREAM and defer:
+        # the weight-gradient slabs leave the critical path: side stream, joined before the pass's slab reduction
+        split_backward(lib, x, w, dy, dx, E, part, S.count)
     else:
-        y_bn, out_bn, saved_bn = sums_for
-        n_part = lib.sgmcmc_conv3x3_stat_slices(n, c, hw)
-        partial = torch.empty((c, n_part, 2), dtype=torch.float64, device=x.device)
-        E = _hip.ConvBwdEpilogue(s_y=y_bn.data_ptr(), s_out=out_bn.data_ptr(), s_mean=saved_bn[0].data_ptr(),
-                                 s_invstd=saved_bn[1].data_ptr(), s_partial=partial.data_ptr(),
-                                 group_imgs=_group_imgs(n), mask_dx=int(_bnlink.PREMASK))
-        from . import bn as _bn
-        E.wrw_mult = WRW_GROUP_MULT and _bn.groups()
-        err = bwd_ex(lib, x, w, dy, dx, E, dw, scratch, slabs if defer else None, _stream(), riders)
+        # (slab reductions pending from earlier launches of this pass ride in this one: take_riders)
+        err = bwd_ex(lib, x, w, dy, dx, E, None, part, S.count, s, take_riders(c, hw))
+        if err:
+            _hip.check(err, "sgmcmc_conv3x3_bwd_ex")
+    return dx, S.finish(part, torch.empty_like(w), 9), partial, n_partials
+
+
+def _both_grads(x, w, dy, sums_for=None):
+    "``sums_for`` = (y_bn, out_bn, saved_bn) of the BatchNorm + ReLU that produced x: its backward sums ride along"
+    from . import bn as _bn
+    dx, dw, partial, n_part = trunk_backward(_hip.lib(), x, w, dy, _stream(), sums_for=sums_for, G=_bn.groups())
+    if partial is not None:
         _bnlink.tag_gradient(dx, partial, n_part, _bnlink.PREMASK)
-    if err:
-        _hip.check(err, "sgmcmc_conv3x3_bwd")
-    if defer:
-        # autograd gets an ALIAS: AccumulateGrad only adopts a gradient nobody else references, and it
-        # must adopt (not copy) this one -- its memory is filled at the end of the pass
-        _pending.append((scratch, dw, slabs.value, 9))     # 3x3 slabs are tap-major (sgmcmc_reduce_job.taps)
-        return dx, dw.view(dw.shape)
     return dx, dw
-
-
-# Weight-gradient slabs whose reduction waits for the end of the running backward pass, where ONE launch
-# sums all of them (autograd's final callback); see ``deferring`` above for when a call may defer.
-_pending = []
 
 
 # ---- riders: pending slab reductions inside the NEXT trunk backward launch (csrc/conv_hip.inc, RideJobs) ------------
@@ -483,15 +535,21 @@ def _join_side():
     _side["keep"].clear()
 
 
+def _reduce_now(entries):
+    "one sgmcmc_wrw_reduce_many launch over ``entries`` (as in ``_pending``) on the current stream"
+    jobs = _fill_jobs((_hip.ReduceJob * len(entries))(), entries)
+    err = _hip.lib().sgmcmc_wrw_reduce_many(ctypes.cast(jobs, ctypes.c_void_p), len(entries), _stream())
+    if err:
+        _hip.check(err, "sgmcmc_wrw_reduce_many")
+
+
 def _flush_pending():
     _join_side()
     if not _pending:
         return
-    jobs = _fill_jobs((_hip.ReduceJob * len(_pending))(), _pending)
-    err = _hip.lib().sgmcmc_wrw_reduce_many(ctypes.cast(jobs, ctypes.c_void_p), len(_pending), _stream())
+    entries = _pending[:]
     _pending.clear()
-    if err:
-        _hip.check(err, "sgmcmc_wrw_reduce_many")
+    _reduce_now(entries)
 
 
 class _Conv3x3(torch.autograd.Function):
@@ -515,11 +573,8 @@ class _Conv3x3(torch.autograd.Function):
             return None, None, None, None, None
         dy = dy.contiguous()
         if ctx.needs_input_grad[0] and ctx.needs_input_grad[1]:
-            defer = _may_defer(w)
-            if defer:   # every deferring call queues it; the first one to run does the work
-                torch.autograd.Variable._execution_engine.queue_callback(_flush_pending)
             # one launch for the two of them (+ the sums of the BatchNorm that produced x, if x is tagged)
-            return (*_both_grads(x, w, dy, defer, None if src_y is None else (src_y, x, src_saved)), None, None, None)
+            return (*_both_grads(x, w, dy, None if src_y is None else (src_y, x, src_saved)), None, None, None)
         dx = _run(dy, w, True)[0] if ctx.needs_input_grad[0] else None
         dw = _weight_grad(x, dy, w) if ctx.needs_input_grad[1] else None
         return dx, dw, None, None, None
@@ -618,33 +673,23 @@ class _ConvDown(torch.autograd.Function):
         scratch = torch.empty(lib.sgmcmc_conv_down_scratch_floats(n, c, hw), dtype=torch.float32, device=x.device)
         dx = torch.empty_like(x)
         dwm, dws = torch.empty_like(w_main), torch.empty_like(w_short)
-        defer = _may_defer(w_main, w_short)
-        slabs = ctypes.c_int(0)
-        if defer:
-            torch.autograd.Variable._execution_engine.queue_callback(_flush_pending)
+        S = slabs_for(w_main, w_short)
         if src_y is None:
             err = lib.sgmcmc_conv_down_bwd(x.data_ptr(), w_main.data_ptr(), w_short.data_ptr(), dym.data_ptr(),
                                            dys.data_ptr(), dx.data_ptr(), dwm.data_ptr(), dws.data_ptr(),
-                                           scratch.data_ptr(), n, c, hw, ctypes.byref(slabs) if defer else None,
-                                           _stream())
+                                           scratch.data_ptr(), n, c, hw, S.ref, _stream())
         else:       # x came out of a BatchNorm + ReLU: that BatchNorm's backward sums ride in this launch (bnlink)
             n_part = lib.sgmcmc_conv_down_bwd_sum_slices(n, c, hw)
             partial = torch.empty((c, n_part, 2), dtype=torch.float64, device=x.device)
-            E = _hip.ConvBwdEpilogue(s_y=src_y.data_ptr(), s_out=x.data_ptr(), s_mean=src_saved[0].data_ptr(),
-                                     s_invstd=src_saved[1].data_ptr(), s_partial=partial.data_ptr(),
-                                     group_imgs=_group_imgs(n), mask_dx=int(_bnlink.PREMASK))
+            E = sums_epilogue(_hip.ConvBwdEpilogue(), src_y, x, src_saved, partial, _group_imgs(n))
             err = lib.sgmcmc_conv_down_bwd_ex(x.data_ptr(), w_main.data_ptr(), w_short.data_ptr(), dym.data_ptr(),
                                               dys.data_ptr(), dx.data_ptr(), ctypes.byref(E), dwm.data_ptr(),
-                                              dws.data_ptr(), scratch.data_ptr(), n, c, hw,
-                                              ctypes.byref(slabs) if defer else None, _stream())
+                                              dws.data_ptr(), scratch.data_ptr(), n, c, hw, S.ref, _stream())
             _bnlink.tag_gradient(dx, partial, n_part, _bnlink.PREMASK)
         if err:
             _hip.check(err, "sgmcmc_conv_down_bwd")
-        if defer:   # scratch = [slabs][dwm.numel()] then [slabs][dws.numel()]
-            _pending.append((scratch, dwm, slabs.value, 9))
-            _pending.append((scratch[slabs.value * dwm.numel():], dws, slabs.value, 1))
-            return dx, dwm.view(dwm.shape), dws.view(dws.shape), None, None, None
-        return dx, dwm, dws, None, None, None
+        # scratch = [slabs][dwm.numel()] then [slabs][dws.numel()]
+        return (dx, S.hand(scratch, dwm, 9), S.hand(scratch[S.count.value * dwm.numel():], dws, 1), None, None, None)
 
 
 def conv_down(x, w_main, w_short, want_stats=False):
@@ -695,18 +740,11 @@ class _ConvStem(torch.autograd.Function):
         n = x.shape[0]
         scratch = torch.empty(lib.sgmcmc_conv_stem_scratch_floats(n), dtype=torch.float32, device=x.device)
         dw = torch.empty_like(w)
-        defer = _may_defer(w)
-        slabs = ctypes.c_int(0)
-        if defer:
-            torch.autograd.Variable._execution_engine.queue_callback(_flush_pending)
-        err = lib.sgmcmc_conv_stem_wrw(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), scratch.data_ptr(), n,
-                                       ctypes.byref(slabs) if defer else None, _stream())
+        S = slabs_for(w)
+        err = lib.sgmcmc_conv_stem_wrw(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), scratch.data_ptr(), n, S.ref, _stream())
         if err:
             _hip.check(err, "sgmcmc_conv_stem_wrw")
-        if defer:
-            _pending.append((scratch, dw, slabs.value, 1))
-            return None, dw.view(dw.shape), None
-        return None, dw, None
+        return None, S.hand(scratch, dw, 1), None
 
 
 def conv_stem(x, w, want_stats=False):
@@ -747,18 +785,11 @@ class _ConvFirst(torch.autograd.Function):
         n = x.shape[0]
         scratch = torch.empty(lib.sgmcmc_conv_first_scratch_floats(n), dtype=torch.float32, device=x.device)
         dw = torch.empty_like(w)
-        defer = _may_defer(w)
-        slabs = ctypes.c_int(0)
-        if defer:
-            torch.autograd.Variable._execution_engine.queue_callback(_flush_pending)
-        err = lib.sgmcmc_conv_first_wrw(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), scratch.data_ptr(), n,
-                                        ctypes.byref(slabs) if defer else None, _stream())
+        S = slabs_for(w)
+        err = lib.sgmcmc_conv_first_wrw(x.data_ptr(), dy.data_ptr(), dw.data_ptr(), scratch.data_ptr(), n, S.ref, _stream())
         if err:
             _hip.check(err, "sgmcmc_conv_first_wrw")
-        if defer:
-            _pending.append((scratch, dw, slabs.value, 1))
-            return None, dw.view(dw.shape)
-        return None, dw
+        return None, S.hand(scratch, dw, 1)
 
 
 def conv_first(x, w):
@@ -805,23 +836,14 @@ class _ConvFirstPool(torch.autograd.Function):
         scratch = torch.empty(lib.sgmcmc_conv_first_pool_scratch_floats(n), dtype=torch.float32, device=x.device)
         dw = torch.empty_like(w)
         db = torch.empty_like(bias) if want_b else None
-        defer = _may_defer(w) and (not want_b or _may_defer(bias))
-        slabs = ctypes.c_int(0)
-        if defer:
-            torch.autograd.Variable._execution_engine.queue_callback(_flush_pending)
+        S = slabs_for(w, bias) if want_b else slabs_for(w)
         err = lib.sgmcmc_conv_first_pool_bwd(x.data_ptr(), dpooled.data_ptr(), code.data_ptr(), dw.data_ptr(),
                                              0 if db is None else db.data_ptr(), scratch.data_ptr(), n, int(want_b),
-                                             ctypes.byref(slabs) if defer else None, _stream())
+                                             S.ref, _stream())
         if err:
             _hip.check(err, "sgmcmc_conv_first_pool_bwd")
-        if defer:
-            P = slabs.value
-            _pending.append((scratch[:P * 450], dw, P, 1))
-            if want_b:
-                _pending.append((scratch[P * 450:], db, P, 1))
-                return None, dw.view(dw.shape), db.view(db.shape)
-            return None, dw.view(dw.shape), None
-        return None, dw, db
+        P = S.count.value           # scratch = [P][dw.numel()] then [P][50]
+        return None, S.hand(scratch[:P * 450], dw, 1), S.hand(scratch[P * 450:], db, 1) if want_b else None
 
 
 def conv_first_pool(x, w, bias=None):
@@ -874,23 +896,16 @@ class _Conv50(torch.autograd.Function):
         scratch = torch.empty(lib.sgmcmc_conv50_scratch_floats(n), dtype=torch.float32, device=x.device)
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         dw = torch.empty_like(w)
-        defer = _may_defer(w)
-        slabs = ctypes.c_int(0)
-        if defer:
-            torch.autograd.Variable._execution_engine.queue_callback(_flush_pending)
+        S = slabs_for(w)
         if dx is not None and wT is not None:
             err = lib.sgmcmc_conv50_bwd_t(x.data_ptr(), wT.data_ptr(), dy.data_ptr(), dx.data_ptr(), dw.data_ptr(),
-                                          scratch.data_ptr(), n, ctypes.byref(slabs) if defer else None, _stream())
+                                          scratch.data_ptr(), n, S.ref, _stream())
         else:
             err = lib.sgmcmc_conv50_bwd(x.data_ptr(), w.data_ptr(), dy.data_ptr(), 0 if dx is None else dx.data_ptr(),
-                                        dw.data_ptr(), scratch.data_ptr(), n, ctypes.byref(slabs) if defer else None,
-                                        _stream())
+                                        dw.data_ptr(), scratch.data_ptr(), n, S.ref, _stream())
         if err:
             _hip.check(err, "sgmcmc_conv50_bwd")
-        if defer:
-            _pending.append((scratch, dw, slabs.value, 9))
-            return dx, dw.view(dw.shape)
-        return dx, dw
+        return dx, S.hand(scratch, dw, 9)
 
 
 def conv50(x, w):
@@ -936,26 +951,17 @@ class _Conv50Pool(torch.autograd.Function):
         dx, dw = torch.empty_like(x), torch.empty_like(w)
         db = torch.empty_like(bias) if want_b else None
         want_w = ctx.needs_input_grad[1]
-        defer = want_w and _may_defer(w) and (not want_b or _may_defer(bias))
-        slabs = ctypes.c_int(0)
-        if defer:
-            torch.autograd.Variable._execution_engine.queue_callback(_flush_pending)
+        S = slabs_for(*((w, bias) if want_b else (w,)), when=want_w)
         err = lib.sgmcmc_conv50_pool_bwd(x.data_ptr(), ctx.wT.data_ptr(), dpooled.data_ptr(), code.data_ptr(),
                                          dx.data_ptr(), dw.data_ptr(), 0 if db is None else db.data_ptr(),
-                                         scratch.data_ptr(), n, int(want_b), ctypes.byref(slabs) if defer else None,
-                                         _stream())
+                                         scratch.data_ptr(), n, int(want_b), S.ref, _stream())
         if err:
             _hip.check(err, "sgmcmc_conv50_pool_bwd")
         dx = dx if ctx.needs_input_grad[0] else None
         if not want_w:
             return dx, None, db
-        if defer:
-            P = slabs.value
-            _pending.append((scratch[:P * 22500], dw, P, 9))
-            if want_b:
-                _pending.append((scratch[P * 22500:], db, P, 1))
-            return dx, dw.view(dw.shape), None if db is None else db.view(db.shape)
-        return dx, dw, db
+        P = S.count.value           # scratch = [P][dw.numel()] then [P][50]
+        return dx, S.hand(scratch[:P * 22500], dw, 9), S.hand(scratch[P * 22500:], db, 1) if want_b else None
 
 
 def conv50_pool(x, w, bias=None):

@@ -634,18 +634,9 @@ int launch_bwd(const float* x, const float* frag, const float* dy, float* dx, co
   else if (sums) SGMCMC_LAUNCH(k01, grid, block, lds, s, x, frag, dy, dx, part, half, n_img, E);
   else SGMCMC_LAUNCH(k00, grid, block, lds, s, x, frag, dy, dx, part, half, n_img, E);
   const int P = half / (C / 16);
-  if (n_slabs) {
-    *n_slabs = P;
-  } else {
-    for (int t = 0; t < C / 16; ++t)
-      SGMCMC_LAUNCH(conv::wrw_reduce_kernel, dim3((unsigned)conv::reduce_blocks(P, W::SLAB)), dim3(256), 0, s,
-                    part + (size_t)t * P * W::SLAB, P, W::SLAB, dw + (size_t)t * W::SLAB, 9);
-  }
-  return (int)hipGetLastError();
-}
-
-__host__ inline bool shape_ok(int channels, int hw) {
-  return (channels == 16 && hw == 32) || (channels == 32 && hw == 16) || (channels == 64 && hw == 8);
+  conv::SlabSet tiles[C / 16];          // one slab set per 16-output-channel tile
+  for (int t = 0; t < C / 16; ++t) tiles[t] = {part + (size_t)t * P * W::SLAB, W::SLAB, dw + (size_t)t * W::SLAB, 9};
+  return conv::finish_slabs(n_slabs, P, s, tiles, C / 16);
 }
 
 }  // namespace conv2
@@ -674,12 +665,12 @@ extern "C" int sgmcmc_conv3x3_prepare_weights(const sgmcmc_frag_job* jobs, int n
 
 extern "C" int sgmcmc_conv3x3_frag_stat_slices(int n_img, int channels, int hw) {
   SGMCMC_FRESH_ERROR_STATE();
-  if (!conv2::shape_ok(channels, hw) || n_img <= 0) return -1;
+  if (!conv::is_trunk_shape(channels, hw) || n_img <= 0) return -1;
   return n_img * (hw / conv2::kRows);
 }
 
 extern "C" int64_t sgmcmc_conv3x3_frag_scratch_floats(int n_img, int channels, int hw) {
-  if (!conv2::shape_ok(channels, hw) || n_img <= 0) return -1;
+  if (!conv::is_trunk_shape(channels, hw) || n_img <= 0) return -1;
   const int half = channels == 16 ? conv2::half_grid<16, 32>(n_img) : channels == 32 ? conv2::half_grid<32, 16>(n_img)
                                                                                       : conv2::half_grid<64, 8>(n_img);
   return (int64_t)half * 144 * channels;
@@ -689,11 +680,7 @@ extern "C" int sgmcmc_conv3x3_frag_fwd(const float* x, const float* frag_fwd, fl
                                        double* stats, void* stream) {
   SGMCMC_FRESH_ERROR_STATE();
   if (!x || !frag_fwd || !y || n_img <= 0) return (int)hipErrorInvalidValue;
-  hipStream_t s = (hipStream_t)stream;
-  if (channels == 16 && hw == 32) return conv2::launch_fwd<16, 32>(x, frag_fwd, y, n_img, stats, s);
-  if (channels == 32 && hw == 16) return conv2::launch_fwd<32, 16>(x, frag_fwd, y, n_img, stats, s);
-  if (channels == 64 && hw == 8) return conv2::launch_fwd<64, 8>(x, frag_fwd, y, n_img, stats, s);
-  return (int)hipErrorInvalidValue;
+  SGMCMC_FOR_TRUNK_SHAPE(channels, hw, conv2::launch_fwd<C, HW>(x, frag_fwd, y, n_img, stats, (hipStream_t)stream));
 }
 
 extern "C" int sgmcmc_conv3x3_frag_bwd(const float* x, const float* frag_dgrad, const float* dy, float* dx,
@@ -702,23 +689,9 @@ extern "C" int sgmcmc_conv3x3_frag_bwd(const float* x, const float* frag_dgrad, 
   SGMCMC_FRESH_ERROR_STATE();
   if (!x || !frag_dgrad || !dy || !dx || !scratch || n_img <= 0 || (!dw && !deferred_slabs)) return (int)hipErrorInvalidValue;
   conv::BwdEpilogue E{};
-  if (epi) {
-    if (epi->e_out && !epi->e_dout) return (int)hipErrorInvalidValue;      // (e_dout alone: added unmasked)
-    const bool sums = epi->s_partial != nullptr;
-    if (sums && (!epi->s_y || !epi->s_out || !epi->s_mean || !epi->s_invstd)) return (int)hipErrorInvalidValue;
-    if (epi->mask_dx && !sums) return (int)hipErrorInvalidValue;
-    E.e_dout = epi->e_dout; E.e_out = epi->e_out;
-    E.mask_dx = epi->mask_dx != 0;
-    if (sums) {
-      E.s_y = epi->s_y; E.s_out = epi->s_out; E.s_mean = epi->s_mean; E.s_invstd = epi->s_invstd; E.s_partial = epi->s_partial;
-      if (epi->group_imgs < 0 || (epi->group_imgs > 0 && n_img % epi->group_imgs)) return (int)hipErrorInvalidValue;
-      conv::set_groups(E, epi->group_imgs);
-    }
-  }
-  hipStream_t s = (hipStream_t)stream;
-  if (channels == 16 && hw == 32) return conv2::launch_bwd<16, 32>(x, frag_dgrad, dy, dx, E, dw, scratch, n_img, deferred_slabs, s);
-  if (channels == 32 && hw == 16) return conv2::launch_bwd<32, 16>(x, frag_dgrad, dy, dx, E, dw, scratch, n_img, deferred_slabs, s);
-  if (channels == 64 && hw == 8) return conv2::launch_bwd<64, 8>(x, frag_dgrad, dy, dx, E, dw, scratch, n_img, deferred_slabs, s);
-  return (int)hipErrorInvalidValue;
+  if (epi)
+    if (const int bad = conv::epilogue_from_abi(epi, n_img, E)) return bad;
+  SGMCMC_FOR_TRUNK_SHAPE(channels, hw, conv2::launch_bwd<C, HW>(x, frag_dgrad, dy, dx, E, dw, scratch, n_img, deferred_slabs,
+                                                                (hipStream_t)stream));
 }
 

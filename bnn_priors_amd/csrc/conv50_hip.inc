@@ -120,11 +120,6 @@ struct PoolArgs {
   float* dbias_part;          // weight-gradient workgroups: [pair of images][50] partial sums (may be NULL)
 };
 
-__device__ __forceinline__ void put_window(float* __restrict__ dst, int pitch, float d, int k) {
-  *reinterpret_cast<float2*>(dst) = make_float2(k == 0 ? d : 0.f, k == 1 ? d : 0.f);
-  *reinterpret_cast<float2*>(dst + pitch) = make_float2(k == 2 ? d : 0.f, k == 3 ? d : 0.f);
-}
-
 template <int CS>
 struct PooledStage {
   static constexpr int TOTAL = C * PCELLS, IT = (TOTAL + T - 1) / T;
@@ -145,7 +140,7 @@ struct PooledStage {
       const int i = (int)threadIdx.x + it * T;
       if (i < TOTAL) {
         const int ci = i / PCELLS, cell = i % PCELLS, oi = cell / PH, oj = cell % PH;
-        put_window(in_s + ci * CS + (2 * oi + 1) * WP + 4 + 2 * oj, WP, (k[it] & 4) ? d[it] : 0.f, k[it] & 3);
+        conv::unpool_window(in_s + ci * CS + (2 * oi + 1) * WP + 4 + 2 * oj, WP, d[it], k[it]);
       }
     }
   }
@@ -282,15 +277,10 @@ __device__ __forceinline__ void conv_body(int b, int n_blocks, const float* __re
       const float* __restrict__ src = y_s + cl * YS + 2 * oi * HW + 2 * oj;
       const float2 r0 = *reinterpret_cast<const float2*>(src);
       const float2 r1 = *reinterpret_cast<const float2*>(src + HW);
-      float m = r0.x;
-      int k = 0;
-      if (r0.y > m || r0.y != r0.y) { m = r0.y; k = 1; }
-      if (r1.x > m || r1.x != r1.x) { m = r1.x; k = 2; }
-      if (r1.y > m || r1.y != r1.y) { m = r1.y; k = 3; }
-      const float tv = m + (pa.bias ? pa.bias[c] : 0.f);
       const size_t o = ((size_t)img * C + c) * PCELLS + cell;
-      pa.pooled[o] = tv > 0.f ? tv : (tv != tv ? tv : 0.f);
-      pa.code[o] = (uint8_t)(k | (tv > 0.f ? 4 : 0));
+      int k;
+      pa.pooled[o] = conv::pool_window(r0, r1, pa.bias ? pa.bias[c] : 0.f, &k);
+      pa.code[o] = (uint8_t)k;
     }
   } else if (co < C) {
     float* __restrict__ yo = y + ((size_t)img * C + co) * NPIX;
@@ -385,9 +375,7 @@ __device__ __forceinline__ void wrw_body(int b, const float* __restrict__ x, con
         const int i = tid + r * T;
         if (i < NDP) {
           const int cl = i / PCELLS, cell = i % PCELLS, oi = cell / PH, oj = cell % PH;
-          const float d = (pk[r] & 4) ? pd[r] : 0.f;
-          put_window(dy_s + cl * DS + 2 * oi * HW + 2 * oj, HW, d, pk[r] & 3);
-          db_s[i] = d;
+          db_s[i] = conv::unpool_window(dy_s + cl * DS + 2 * oi * HW + 2 * oj, HW, pd[r], pk[r]);
         }
       }
     } else {
@@ -546,13 +534,7 @@ extern "C" int sgmcmc_conv50_bwd(const float* x, const float* w, const float* dy
   } else {
     SGMCMC_LAUNCH(conv50::wrw_kernel, dim3((unsigned)n_wrw), dim3(conv50::T), conv50::LDS_W, s, x, dy, scratch, n_img);
   }
-  if (deferred_slabs) {
-    *deferred_slabs = P;
-  } else {
-    const int E = conv50::C * conv50::C * 9;
-    SGMCMC_LAUNCH(conv::wrw_reduce_kernel, dim3((unsigned)conv::reduce_blocks(P, E)), dim3(256), 0, s, scratch, P, E, dw, 9);
-  }
-  return (int)hipGetLastError();
+  return conv::finish_slabs(deferred_slabs, P, s, {{scratch, conv50::C * conv50::C * 9, dw, 9}});
 }
 
 // as sgmcmc_conv50_bwd with the data gradient's weights prepared by sgmcmc_conv50_fwd (wT): dx required
@@ -566,13 +548,7 @@ extern "C" int sgmcmc_conv50_bwd_t(const float* x, const float* wT, const float*
   const size_t lds = conv50::LDS_FWD > conv50::LDS_W ? conv50::LDS_FWD : conv50::LDS_W;
   SGMCMC_LAUNCH(conv50::bwd_t_kernel, dim3((unsigned)(n_wrw + n_img * conv50::NSUB)), dim3(conv50::T), lds, s, x, wT, dy, dx,
                 scratch, n_wrw, n_img);
-  if (deferred_slabs) {
-    *deferred_slabs = P;
-  } else {
-    const int E = conv50::C * conv50::C * 9;
-    SGMCMC_LAUNCH(conv::wrw_reduce_kernel, dim3((unsigned)conv::reduce_blocks(P, E)), dim3(256), 0, s, scratch, P, E, dw, 9);
-  }
-  return (int)hipGetLastError();
+  return conv::finish_slabs(deferred_slabs, P, s, {{scratch, conv50::C * conv50::C * 9, dw, 9}});
 }
 
 /* the layer WITH its tail, Conv2d(50, 50, 3, padding=1) -> + bias -> ReLU -> MaxPool2d(2): pooled [n][50][7][7],
@@ -609,13 +585,6 @@ extern "C" int sgmcmc_conv50_pool_bwd(const float* x, const float* wT, const flo
   const conv50::PoolArgs pa = {nullptr, nullptr, nullptr, code, bpart};
   SGMCMC_LAUNCH(conv50::bwd_pool_kernel, dim3((unsigned)(n_wrw + n_img * conv50::NSUB)), dim3(conv50::T), lds, s, x, wT,
                 dpooled, dx, scratch, n_wrw, n_img, pa);
-  if (deferred_slabs) {
-    *deferred_slabs = P;
-  } else {
-    SGMCMC_LAUNCH(conv::wrw_reduce_kernel, dim3((unsigned)conv::reduce_blocks(P, E)), dim3(256), 0, s, scratch, P, E, dw, 9);
-    if (want_bias)
-      SGMCMC_LAUNCH(conv::wrw_reduce_kernel, dim3((unsigned)conv::reduce_blocks(P, conv50::C)), dim3(256), 0, s, bpart, P,
-                    conv50::C, dbias, 1);
-  }
-  return (int)hipGetLastError();
+  return conv::finish_slabs(deferred_slabs, P, s,
+                            {{scratch, E, dw, 9}, {bpart, conv50::C, want_bias ? dbias : nullptr, 1}});
 }

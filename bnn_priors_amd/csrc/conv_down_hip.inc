@@ -491,15 +491,7 @@ int launch_bwd(const float* x, const float* wm, const float* ws, const float* dy
                                  part_m, part_s, n_dgrad, n_items, Ev);
   else SGMCMC_LAUNCH(k, dim3((unsigned)(n_dgrad + P * W::CT)), dim3(256), lds, s, x, wm, ws, dym, dys, dx, part_m,
                      part_s, n_dgrad, n_items, Ev);
-  if (n_slabs) {
-    *n_slabs = P;
-  } else {
-    SGMCMC_LAUNCH(conv::wrw_reduce_kernel, dim3((unsigned)conv::reduce_blocks(P, W::E_MAIN)), dim3(256), 0, s, part_m,
-                       P, W::E_MAIN, dwm, 9);
-    SGMCMC_LAUNCH(conv::wrw_reduce_kernel, dim3((unsigned)conv::reduce_blocks(P, W::E_SHORT)), dim3(256), 0, s, part_s,
-                       P, W::E_SHORT, dws, 1);
-  }
-  return (int)hipGetLastError();
+  return conv::finish_slabs(n_slabs, P, s, {{part_m, W::E_MAIN, dwm, 9}, {part_s, W::E_SHORT, dws, 1}});
 }
 
 }  // namespace convdown
@@ -536,14 +528,9 @@ extern "C" int sgmcmc_conv_down_bwd_ex(const float* x, const float* w_main, cons
   if (!x || !w_main || !w_short || !dy_main || !dy_short || !dx || !scratch || n_img <= 0 || !epi ||
       (!deferred_slabs && (!dw_main || !dw_short)))
     return (int)hipErrorInvalidValue;
-  if (epi->e_dout || epi->e_out || !epi->s_partial || !epi->s_y || !epi->s_out || !epi->s_mean || !epi->s_invstd)
-    return (int)hipErrorInvalidValue;     // only the SUMS half of the epilogue exists here
-  conv::BwdEpilogue E{};
-  E.s_y = epi->s_y; E.s_out = epi->s_out; E.s_mean = epi->s_mean; E.s_invstd = epi->s_invstd;
-  E.s_partial = epi->s_partial;
-  E.mask_dx = epi->mask_dx != 0;
-  if (epi->group_imgs < 0 || (epi->group_imgs > 0 && n_img % epi->group_imgs)) return (int)hipErrorInvalidValue;
-  conv::set_groups(E, epi->group_imgs);
+  if (epi->e_dout || epi->e_out || !epi->s_partial) return (int)hipErrorInvalidValue;     // only the SUMS half exists here
+  conv::BwdEpilogue E;
+  if (const int bad = conv::epilogue_from_abi(epi, n_img, E)) return bad;
   hipStream_t s = (hipStream_t)stream;
   if (cin == 16 && hwi == 32)
     return convdown::launch_bwd<16, 32>(x, w_main, w_short, dy_main, dy_short, dx, dw_main, dw_short, scratch,
@@ -726,13 +713,7 @@ extern "C" int sgmcmc_conv_stem_wrw(const float* x, const float* dy, float* dw, 
   hipStream_t s = (hipStream_t)stream;
   const int n_items = n_img * convstem::BANDS, P = (n_items + 1) / 2;
   SGMCMC_LAUNCH(convstem::wrw_kernel, dim3((unsigned)P), dim3(256), 0, s, x, dy, scratch, n_items);
-  if (deferred_slabs) {
-    *deferred_slabs = P;
-  } else {
-    const int E = convstem::COUT * convstem::K;
-    SGMCMC_LAUNCH(conv::wrw_reduce_kernel, dim3((unsigned)conv::reduce_blocks(P, E)), dim3(256), 0, s, scratch, P, E, dw, 1);
-  }
-  return (int)hipGetLastError();
+  return conv::finish_slabs(deferred_slabs, P, s, {{scratch, convstem::COUT * convstem::K, dw, 1}});
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -760,10 +741,23 @@ __device__ __forceinline__ void stage(float* __restrict__ in_s, const float* __r
 
 __device__ __forceinline__ int tap_offset(int kidx) { return (kidx / 3) * WP + kidx % 3; }
 
-__global__ __launch_bounds__(256) void fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                  float* __restrict__ y) {
+// ---- the first layer WITH its tail: conv -> + bias -> ReLU -> MaxPool2d(2) in one launch each way ---------------
+// (conv_nets.py:46-57: Conv2d(1, 50, 3, padding=1), ReLU, MaxPool2d(2).)  The 50 x 28 x 28 map (20 MB per batch of
+// 128) never reaches memory: the forward leaves the pooled 50 x 14 x 14 map and ONE BYTE per pooled element
+// (conv::pool_window) and the backward rebuilds the band's dense dy in LDS from the pooled gradient and that byte
+// (conv::unpool_window), then runs the same weight-gradient contraction (same operands, same order, same bits); the bias
+// gradient's per-band partial sums leave with the slabs.
+constexpr int YS = NPIX + 4, PW = HW / 2, PCELLS = (ROWS / 2) * PW;   // 28 pooled cells per channel and band
+
+// The forward of one (image, band) workgroup.  POOL_EPI: the tiles go to LDS and leave through + bias -> ReLU ->
+// MaxPool2d(2) as (pooled, code); else they are stored to y.
+template <bool POOL_EPI>
+__device__ __forceinline__ void fwd_body(const float* __restrict__ x, const float* __restrict__ w, float* __restrict__ y,
+                                         const float* __restrict__ bias, float* __restrict__ pooled,
+                                         uint8_t* __restrict__ code) {
   const int bid = conv::xcd_remap((int)blockIdx.x, (int)gridDim.x);      // XCD-aware block order (round 6)
   __shared__ float in_s[CS];
+  __shared__ __attribute__((aligned(16))) float y_s[POOL_EPI ? COUT * YS : 4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int band = bid % BANDS, img = bid / BANDS, y0 = band * ROWS;
   stage(in_s, x + (size_t)img * HW * HW, y0, tid);
@@ -786,26 +780,84 @@ __global__ __launch_bounds__(256) void fwd_kernel(const float* __restrict__ x, c
 #pragma unroll
     for (int kk = 0; kk < KSTEPS; ++kk)
       acc = __builtin_amdgcn_mfma_f32_16x16x4f32(in_s[base + aoff[kk]], breg[kk], acc, 0, 0, 0);
-    if (co < COUT)   // D rows 4kq .. 4kq+3 = 4 consecutive pixels of the band (row-major: contiguous in memory)
-      sgmcmc_store4<4>(y, y + ((size_t)img * COUT + co) * HW * HW + (size_t)y0 * HW + 16 * t + 4 * kq, acc[0], acc[1], acc[2], acc[3]);
+    if (co < COUT) {   // D rows 4kq .. 4kq+3 = 4 consecutive pixels of the band (row-major: contiguous in memory)
+      if constexpr (POOL_EPI)
+        *reinterpret_cast<float4*>(y_s + co * YS + 16 * t + 4 * kq) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+      else
+        sgmcmc_store4<4>(y, y + ((size_t)img * COUT + co) * HW * HW + (size_t)y0 * HW + 16 * t + 4 * kq, acc[0], acc[1], acc[2], acc[3]);
+    }
   }
+  if constexpr (POOL_EPI) {
+    __syncthreads();
+    for (int i = tid; i < COUT * PCELLS; i += 256) {
+      const int c = i / PCELLS, q = i % PCELLS, oi = q / PW, oj = q % PW;
+      const float* __restrict__ src = y_s + c * YS + 2 * oi * HW + 2 * oj;
+      const float2 r0 = *reinterpret_cast<const float2*>(src);
+      const float2 r1 = *reinterpret_cast<const float2*>(src + HW);
+      const size_t o = (((size_t)img * COUT + c) * PW + (y0 >> 1) + oi) * PW + oj;
+      int k;
+      pooled[o] = conv::pool_window(r0, r1, bias ? bias[c] : 0.f, &k);
+      code[o] = (uint8_t)k;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                  float* __restrict__ y) {
+  fwd_body<false>(x, w, y, nullptr, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(256) void fwd_pool_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                       const float* __restrict__ bias, float* __restrict__ pooled,
+                                                       uint8_t* __restrict__ code) {
+  fwd_body<true>(x, w, nullptr, bias, pooled, code);
 }
 
 // dw[co][tap] slabs, one per (image, band): wave = channel tile; per 4-pixel k-step one A fetch (dy) and one B fetch
 // (the lane's tap of x).  (One workgroup per image walking its 7 bands paid 7 serialised load latencies on half
-// of the CUs: 16.4 us; a workgroup per band pays one.)
-__global__ __launch_bounds__(256) void wrw_kernel(const float* __restrict__ x, const float* __restrict__ dy,
-                                                  float* __restrict__ part) {
+// of the CUs: 16.4 us; a workgroup per band pays one.)  FROM_POOLED: dy is the gradient of the POOLED map and `code` its
+// bytes -- the band's dense dy is rebuilt in LDS -- and dbias_part (may be NULL) takes the band's bias-gradient partials.
+template <bool FROM_POOLED>
+__device__ __forceinline__ void wrw_body(const float* __restrict__ x, const float* __restrict__ dy,
+                                         const uint8_t* __restrict__ code, float* __restrict__ part,
+                                         float* __restrict__ dbias_part) {
   const int bid = conv::xcd_remap((int)blockIdx.x, (int)gridDim.x);      // XCD-aware block order (round 6)
   constexpr int DS = NPIX + 4;
   __shared__ float in_s[CS];
-  __shared__ float dy_s[CT * 16 * DS];
+  __shared__ __attribute__((aligned(16))) float dy_s[CT * 16 * DS];
+  __shared__ float d_s[FROM_POOLED ? COUT * PCELLS : 1];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int band = bid % BANDS, img = bid / BANDS, n = lane & 15, kq = lane >> 4;
-  const int off = tap_offset(n < K ? n : 0);
+  const int off = tap_offset(n < K ? n : 0), y0 = band * ROWS;
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  {
-    const int y0 = band * ROWS;
+  if constexpr (FROM_POOLED) {
+    // the band's pooled gradients and bytes first (the only loads that the contraction waits for), x next to them
+    constexpr int PER = (COUT * PCELLS + 255) / 256;
+    float dreg[PER];
+    uint8_t creg[PER];
+#pragma unroll
+    for (int r = 0; r < PER; ++r) {
+      const int i = tid + 256 * r;
+      dreg[r] = 0.f;
+      creg[r] = 0;
+      if (i < COUT * PCELLS) {
+        const int c = i / PCELLS, q = i % PCELLS;
+        const size_t o = (((size_t)img * COUT + c) * PW + (y0 >> 1)) * PW + q;   // the band's two pooled rows: contiguous
+        dreg[r] = dy[o];
+        creg[r] = code[o];
+      }
+    }
+    stage(in_s, x + (size_t)img * HW * HW, y0, tid);
+    for (int i = tid; i < (CT * 16 - COUT) * DS; i += 256) dy_s[COUT * DS + i] = 0.f;     // the channel padding
+#pragma unroll
+    for (int r = 0; r < PER; ++r) {
+      const int i = tid + 256 * r;
+      if (i < COUT * PCELLS) {
+        const int c = i / PCELLS, q = i % PCELLS, oi = q / PW, oj = q % PW;
+        d_s[i] = conv::unpool_window(dy_s + c * DS + 2 * oi * HW + 2 * oj, HW, dreg[r], creg[r]);
+      }
+    }
+  } else {
     float4 rd[(CT * 16 * NPIX / 4 + 255) / 256];
     conv::stage_load<CT * 16 * NPIX / 4, float4>(rd, [&](int i) {
       const int v = i % (NPIX / 4), c = i / (NPIX / 4);
@@ -819,13 +871,13 @@ __global__ __launch_bounds__(256) void wrw_kernel(const float* __restrict__ x, c
       const int v = i % (NPIX / 4), c = i / (NPIX / 4);
       *reinterpret_cast<float4*>(dy_s + c * DS + 4 * v) = val;
     });
-    __syncthreads();
+  }
+  __syncthreads();
 #pragma unroll 4
-    for (int g = 0; g < NPIX / 4; ++g) {
-      const int p = 4 * g + kq;
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(dy_s[(wave * 16 + n) * DS + p],
-                                                 in_s[(p / HW) * WP + p % HW + 3 + off], acc, 0, 0, 0);
-    }
+  for (int g = 0; g < NPIX / 4; ++g) {
+    const int p = 4 * g + kq;
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(dy_s[(wave * 16 + n) * DS + p],
+                                               in_s[(p / HW) * WP + p % HW + 3 + off], acc, 0, 0, 0);
   }
   // D[row = co][col = tap]
   if (n < K) {
@@ -835,127 +887,25 @@ __global__ __launch_bounds__(256) void wrw_kernel(const float* __restrict__ x, c
       if (co < COUT) part[(size_t)bid * (COUT * K) + co * K + n] = acc[v];
     }
   }
+  if constexpr (FROM_POOLED) {
+    if (dbias_part && tid < COUT) {     // the band's share of the bias gradient: its 28 cells in order
+      float sum = 0.f;
+#pragma unroll 4
+      for (int q = 0; q < PCELLS; ++q) sum += d_s[tid * PCELLS + q];
+      dbias_part[(size_t)bid * COUT + tid] = sum;
+    }
+  }
 }
 
-// ---- the first layer WITH its tail: conv -> + bias -> ReLU -> MaxPool2d(2) in one launch each way ---------------
-// (conv_nets.py:46-57: Conv2d(1, 50, 3, padding=1), ReLU, MaxPool2d(2).)  The 50 x 28 x 28 map (20 MB per batch of
-// 128) never reaches memory: the forward leaves the pooled 50 x 14 x 14 map and ONE BYTE per pooled element -- which
-// of the window's four positions held the maximum (bits 0-1: first maximum in scan order, NaNs win, as ATen) and
-// whether it passed the ReLU (bit 2) -- and the backward rebuilds the band's dense dy in LDS from the pooled gradient
-// and that byte, then runs the weight-gradient contraction above unchanged (same operands, same order, same bits);
-// the bias gradient's per-band partial sums leave with the slabs.
-constexpr int YS = NPIX + 4, PW = HW / 2, PCELLS = (ROWS / 2) * PW;   // 28 pooled cells per channel and band
-
-__global__ __launch_bounds__(256) void fwd_pool_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                       const float* __restrict__ bias, float* __restrict__ pooled,
-                                                       uint8_t* __restrict__ code) {
-  const int bid = conv::xcd_remap((int)blockIdx.x, (int)gridDim.x);      // XCD-aware block order (round 6)
-  __shared__ float in_s[CS];
-  __shared__ __attribute__((aligned(16))) float y_s[COUT * YS];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int band = bid % BANDS, img = bid / BANDS, y0 = band * ROWS;
-  stage(in_s, x + (size_t)img * HW * HW, y0, tid);
-  const int n = lane & 15, kq = lane >> 4;
-  int aoff[KSTEPS];
-#pragma unroll
-  for (int kk = 0; kk < KSTEPS; ++kk) aoff[kk] = tap_offset(4 * kk + kq < K ? 4 * kk + kq : 0);
-  __syncthreads();
-  for (int pair = wave; pair < NT * CT; pair += 4) {
-    const int t = pair / CT, ct = pair % CT, co = ct * 16 + n;
-    float breg[KSTEPS];
-#pragma unroll
-    for (int kk = 0; kk < KSTEPS; ++kk) {
-      const int kidx = 4 * kk + kq;
-      breg[kk] = (kidx < K && co < COUT) ? w[co * K + kidx] : 0.f;
-    }
-    const int p = 16 * t + n, base = (p / HW) * WP + p % HW + 3;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int kk = 0; kk < KSTEPS; ++kk)
-      acc = __builtin_amdgcn_mfma_f32_16x16x4f32(in_s[base + aoff[kk]], breg[kk], acc, 0, 0, 0);
-    if (co < COUT)
-      *reinterpret_cast<float4*>(y_s + co * YS + 16 * t + 4 * kq) = make_float4(acc[0], acc[1], acc[2], acc[3]);
-  }
-  __syncthreads();
-  for (int i = tid; i < COUT * PCELLS; i += 256) {
-    const int c = i / PCELLS, q = i % PCELLS, oi = q / PW, oj = q % PW;
-    const float* __restrict__ src = y_s + c * YS + 2 * oi * HW + 2 * oj;
-    const float2 r0 = *reinterpret_cast<const float2*>(src);
-    const float2 r1 = *reinterpret_cast<const float2*>(src + HW);
-    float m = r0.x;
-    int k = 0;
-    if (r0.y > m || r0.y != r0.y) { m = r0.y; k = 1; }
-    if (r1.x > m || r1.x != r1.x) { m = r1.x; k = 2; }
-    if (r1.y > m || r1.y != r1.y) { m = r1.y; k = 3; }
-    const float tv = m + (bias ? bias[c] : 0.f);
-    const size_t o = (((size_t)img * COUT + c) * PW + (y0 >> 1) + oi) * PW + oj;
-    pooled[o] = tv > 0.f ? tv : (tv != tv ? tv : 0.f);
-    code[o] = (uint8_t)(k | (tv > 0.f ? 4 : 0));
-  }
+__global__ __launch_bounds__(256) void wrw_kernel(const float* __restrict__ x, const float* __restrict__ dy,
+                                                  float* __restrict__ part) {
+  wrw_body<false>(x, dy, nullptr, part, nullptr);
 }
 
 __global__ __launch_bounds__(256) void wrw_pool_kernel(const float* __restrict__ x, const float* __restrict__ dpooled,
                                                        const uint8_t* __restrict__ code, float* __restrict__ part,
                                                        float* __restrict__ dbias_part) {
-  const int bid = conv::xcd_remap((int)blockIdx.x, (int)gridDim.x);      // XCD-aware block order (round 6)
-  constexpr int DS = NPIX + 4;
-  __shared__ float in_s[CS];
-  __shared__ __attribute__((aligned(16))) float dy_s[CT * 16 * DS];
-  __shared__ float d_s[COUT * PCELLS];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int band = bid % BANDS, img = bid / BANDS, n = lane & 15, kq = lane >> 4;
-  const int off = tap_offset(n < K ? n : 0), y0 = band * ROWS;
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  // the band's pooled gradients and bytes first (the only loads that the contraction waits for), x next to them
-  constexpr int PER = (COUT * PCELLS + 255) / 256;
-  float dreg[PER];
-  uint8_t creg[PER];
-#pragma unroll
-  for (int r = 0; r < PER; ++r) {
-    const int i = tid + 256 * r;
-    dreg[r] = 0.f;
-    creg[r] = 0;
-    if (i < COUT * PCELLS) {
-      const int c = i / PCELLS, q = i % PCELLS;
-      const size_t o = (((size_t)img * COUT + c) * PW + (y0 >> 1)) * PW + q;   // the band's two pooled rows: contiguous
-      dreg[r] = dpooled[o];
-      creg[r] = code[o];
-    }
-  }
-  stage(in_s, x + (size_t)img * HW * HW, y0, tid);
-  for (int i = tid; i < (CT * 16 - COUT) * DS; i += 256) dy_s[COUT * DS + i] = 0.f;     // the channel padding
-#pragma unroll
-  for (int r = 0; r < PER; ++r) {
-    const int i = tid + 256 * r;
-    if (i < COUT * PCELLS) {
-      const int c = i / PCELLS, q = i % PCELLS, oi = q / PW, oj = q % PW, k = creg[r] & 3;
-      const float d = (creg[r] & 4) ? dreg[r] : 0.f;
-      float* __restrict__ dst = dy_s + c * DS + 2 * oi * HW + 2 * oj;
-      *reinterpret_cast<float2*>(dst) = make_float2(k == 0 ? d : 0.f, k == 1 ? d : 0.f);
-      *reinterpret_cast<float2*>(dst + HW) = make_float2(k == 2 ? d : 0.f, k == 3 ? d : 0.f);
-      d_s[i] = d;
-    }
-  }
-  __syncthreads();
-#pragma unroll 4
-  for (int g = 0; g < NPIX / 4; ++g) {
-    const int p = 4 * g + kq;
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(dy_s[(wave * 16 + n) * DS + p],
-                                               in_s[(p / HW) * WP + p % HW + 3 + off], acc, 0, 0, 0);
-  }
-  if (n < K) {
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      const int co = wave * 16 + 4 * kq + v;
-      if (co < COUT) part[(size_t)bid * (COUT * K) + co * K + n] = acc[v];
-    }
-  }
-  if (dbias_part && tid < COUT) {     // the band's share of the bias gradient: its 28 cells in order
-    float sum = 0.f;
-#pragma unroll 4
-    for (int q = 0; q < PCELLS; ++q) sum += d_s[tid * PCELLS + q];
-    dbias_part[(size_t)bid * COUT + tid] = sum;
-  }
+  wrw_body<true>(x, dpooled, code, part, dbias_part);
 }
 
 }  // namespace convfirst
@@ -979,13 +929,7 @@ extern "C" int sgmcmc_conv_first_wrw(const float* x, const float* dy, float* dw,
   hipStream_t s = (hipStream_t)stream;
   const int P = n_img * convfirst::BANDS;
   SGMCMC_LAUNCH(convfirst::wrw_kernel, dim3((unsigned)P), dim3(256), 0, s, x, dy, scratch);
-  if (deferred_slabs) {
-    *deferred_slabs = P;
-  } else {
-    const int E = convfirst::COUT * convfirst::K;
-    SGMCMC_LAUNCH(conv::wrw_reduce_kernel, dim3((unsigned)conv::reduce_blocks(P, E)), dim3(256), 0, s, scratch, P, E, dw, 1);
-  }
-  return (int)hipGetLastError();
+  return conv::finish_slabs(deferred_slabs, P, s, {{scratch, convfirst::COUT * convfirst::K, dw, 1}});
 }
 
 /* conv_first + bias + ReLU + MaxPool2d(2) in one launch: pooled [n][50][14][14], code [n][50][14][14] bytes */
@@ -1014,13 +958,6 @@ extern "C" int sgmcmc_conv_first_pool_bwd(const float* x, const float* dpooled, 
   const int P = n_img * convfirst::BANDS, E = convfirst::COUT * convfirst::K;
   float* bpart = want_bias ? scratch + (size_t)P * E : nullptr;
   SGMCMC_LAUNCH(convfirst::wrw_pool_kernel, dim3((unsigned)P), dim3(256), 0, s, x, dpooled, code, scratch, bpart);
-  if (deferred_slabs) {
-    *deferred_slabs = P;
-  } else {
-    SGMCMC_LAUNCH(conv::wrw_reduce_kernel, dim3((unsigned)conv::reduce_blocks(P, E)), dim3(256), 0, s, scratch, P, E, dw, 1);
-    if (want_bias)
-      SGMCMC_LAUNCH(conv::wrw_reduce_kernel, dim3((unsigned)conv::reduce_blocks(P, convfirst::COUT)), dim3(256), 0, s,
-                    bpart, P, convfirst::COUT, dbias, 1);
-  }
-  return (int)hipGetLastError();
+  return conv::finish_slabs(deferred_slabs, P, s,
+                            {{scratch, E, dw, 1}, {bpart, convfirst::COUT, want_bias ? dbias : nullptr, 1}});
 }

@@ -51,16 +51,8 @@ extern "C" int sgmcmc_conv3x3_bwd_part(const float* x, const float* w, const flo
   if (which == 1) {            // data gradient (+ epilogues)
     if (!w || !dx) return (int)hipErrorInvalidValue;
     if (epi) {
-      if (epi->e_out && !epi->e_dout) return (int)hipErrorInvalidValue;
-      if (epi->s_partial && (!epi->s_y || !epi->s_out || !epi->s_mean || !epi->s_invstd)) return (int)hipErrorInvalidValue;
-      if (epi->mask_dx && !epi->s_partial) return (int)hipErrorInvalidValue;
-      E.e_dout = epi->e_dout; E.e_out = epi->e_out;
-      E.mask_dx = epi->mask_dx != 0;
-      if (epi->s_partial) {
-        E.s_y = epi->s_y; E.s_out = epi->s_out; E.s_mean = epi->s_mean; E.s_invstd = epi->s_invstd;
-        E.s_partial = epi->s_partial;
-        conv::set_groups(E, epi->group_imgs);
-      }
+      if (const int bad = conv::epilogue_from_abi(epi, n_img, E)) return bad;
+      E.wrw_mult = 0;          // (this half writes no slabs)
     }
   } else if (!x || !scratch || !deferred_slabs) {       // weight-gradient slabs: always left for sgmcmc_wrw_reduce_many
     return (int)hipErrorInvalidValue;
@@ -79,10 +71,7 @@ extern "C" int sgmcmc_conv3x3_fx(const float* x, const float* w, float* y, int n
   if (!x || !w || !y || !fx || n_img <= 0) return (int)hipErrorInvalidValue;
   hipStream_t s = (hipStream_t)stream;
   long long* f = reinterpret_cast<long long*>(fx);
-  if (channels == 16 && hw == 32) return conv::launch_conv3x3_fold<16, 32, 8>(x, w, y, n_img, f, nullptr, nullptr, s);
-  if (channels == 32 && hw == 16) return conv::launch_conv3x3_fold<32, 16, 8>(x, w, y, n_img, f, nullptr, nullptr, s);
-  if (channels == 64 && hw == 8) return conv::launch_conv3x3_fold<64, 8, 8>(x, w, y, n_img, f, nullptr, nullptr, s);
-  return (int)hipErrorInvalidValue;
+  SGMCMC_FOR_TRUNK_SHAPE(channels, hw, conv::launch_conv3x3_fold<C, HW, ROWS>(x, w, y, n_img, f, nullptr, nullptr, s));
 }
 
 /* y = conv3x3(relu(BatchNorm(x)), w): the BatchNorm (training mode, batch statistics from bn->fx as left by
@@ -98,9 +87,6 @@ extern "C" int sgmcmc_conv3x3_bnin(const float* x, const float* w, float* y, int
   const conv::BnIn B = {reinterpret_cast<const long long*>(bn->fx), bn->gamma, bn->beta, bn->save_mean, bn->save_invstd,
                         bn->running_mean, bn->running_var, bn->stat_log, bn->momentum, bn->eps,
                         (double)n_img * hw * hw, bn->h};
-  if (channels == 16 && hw == 32) return conv::launch_conv3x3_fold<16, 32, 8>(x, w, y, n_img, nullptr, stats, &B, s);
-  if (channels == 32 && hw == 16) return conv::launch_conv3x3_fold<32, 16, 8>(x, w, y, n_img, nullptr, stats, &B, s);
-  if (channels == 64 && hw == 8) return conv::launch_conv3x3_fold<64, 8, 8>(x, w, y, n_img, nullptr, stats, &B, s);
-  return (int)hipErrorInvalidValue;
+  SGMCMC_FOR_TRUNK_SHAPE(channels, hw, conv::launch_conv3x3_fold<C, HW, ROWS>(x, w, y, n_img, nullptr, stats, &B, s));
 }
 

@@ -334,8 +334,7 @@ int launch_fused_bwd(const float* x, const float* w, float* dx, float* part, con
   const dim3 grid((unsigned)(n_dgrad + P * G::CT)), block(256);
   if (B.e_dout) SGMCMC_LAUNCH(k1, grid, block, lds, s, x, w, dx, part, B, n_dgrad, n_items);
   else SGMCMC_LAUNCH(k0, grid, block, lds, s, x, w, dx, part, B, n_dgrad, n_items);
-  *n_slabs = P;
-  return (int)hipGetLastError();
+  return finish_slabs(n_slabs, P, s, {});      // (always left to the caller: n_slabs is required)
 }
 
 }  // namespace conv
@@ -354,8 +353,5 @@ extern "C" int sgmcmc_conv3x3_bn_bwd(const float* x, const float* w, float* dx, 
   B.dout = A->dout; B.mask_out = A->mask_out; B.y = A->y; B.mean = A->mean; B.invstd = A->invstd; B.gamma = A->gamma;
   B.sums = A->sums; B.n_sums = A->n_sums; B.count = (double)n_img * hw * hw; B.dgamma = A->dgamma; B.dbeta = A->dbeta;
   B.e_dout = A->e_dout; B.e_out = A->e_out;
-  if (channels == 16 && hw == 32) return conv::launch_fused_bwd<16, 32, 8>(x, w, dx, scratch, B, n_img, n_slabs, s);
-  if (channels == 32 && hw == 16) return conv::launch_fused_bwd<32, 16, 8>(x, w, dx, scratch, B, n_img, n_slabs, s);
-  if (channels == 64 && hw == 8) return conv::launch_fused_bwd<64, 8, 8>(x, w, dx, scratch, B, n_img, n_slabs, s);
-  return (int)hipErrorInvalidValue;
+  SGMCMC_FOR_TRUNK_SHAPE(channels, hw, conv::launch_fused_bwd<C, HW, ROWS>(x, w, dx, scratch, B, n_img, n_slabs, s));
 }

@@ -253,6 +253,30 @@ __device__ __forceinline__ void band_sums(float s1, float s2, float* __restrict_
   }
 }
 
+// ---- + bias -> ReLU -> MaxPool2d(2): ONE 2 x 2 window, for every kernel that pools (pool_hip.inc, convfirst, conv50) ----
+// pool_window: the window's rows r0, r1 and the channel's bias -> relu(max + bias) and the window's byte: bits 0-1 the
+// position of the FIRST maximum in scan order (0,0), (0,1), (1,0), (1,1) -- strict comparisons, NaNs win and propagate,
+// as ATen's max_pool2d / relu -- bit 2 whether max + bias passed the ReLU.
+__device__ __forceinline__ float pool_window(const float2 r0, const float2 r1, float bias, int* code) {
+  float m = r0.x;
+  int k = 0;
+  if (r0.y > m || r0.y != r0.y) { m = r0.y; k = 1; }
+  if (r1.x > m || r1.x != r1.x) { m = r1.x; k = 2; }
+  if (r1.y > m || r1.y != r1.y) { m = r1.y; k = 3; }
+  const float tv = m + bias;
+  *code = k | (tv > 0.f ? 4 : 0);
+  return tv > 0.f ? tv : (tv != tv ? tv : 0.f);
+}
+// ... and its inverse: the window of the gradient, written whole (rows `pitch` apart) -- the pooled cell's gradient at
+// the position the byte names if that cell passed the ReLU, zeros elsewhere; -> the gradient that was routed
+__device__ __forceinline__ float unpool_window(float* __restrict__ dst, int pitch, float dpooled, int code) {
+  const float d = (code & 4) ? dpooled : 0.f;
+  const int k = code & 3;
+  *reinterpret_cast<float2*>(dst) = make_float2(k == 0 ? d : 0.f, k == 1 ? d : 0.f);
+  *reinterpret_cast<float2*>(dst + pitch) = make_float2(k == 2 ? d : 0.f, k == 3 ? d : 0.f);
+  return d;
+}
+
 // what the data gradient's epilogue may do besides storing dx (all pointers device; null = not requested)
 struct BwdEpilogue {
   const float* e_dout;    // ADD: dx += e_dout * [e_out > 0]  (identity shortcut's gradient); e_out NULL: e_dout arrives
@@ -1047,6 +1071,65 @@ __global__ __launch_bounds__(256, (MULT || C >= 64) ? 2 : 3) void conv3x3_bwd_ke
   else conv3x3_body<C, HW, ROWS, true, false, EPI, SUMS>(xcd_remap<C>(b - n_wrw, n_dgrad), dy, w, dx, nullptr, 0, &E);
 }
 
+// ---- host-side pieces every convolution entry point shares -----------------------------------------------------
+// The trunk's shape table, in ONE place: `return <expression>;` with constexpr C, HW, ROWS of (channels, hw), or the
+// refusal (the caller keeps other shapes on the library path).
+inline bool is_trunk_shape(int channels, int hw) {
+  return (channels == 16 && hw == 32) || (channels == 32 && hw == 16) || (channels == 64 && hw == 8);
+}
+#define SGMCMC_FOR_TRUNK_SHAPE(channels, hw, ...)                                                                     \
+  do {                                                                                                                \
+    if ((channels) == 16 && (hw) == 32) { constexpr int C = 16, HW = 32, ROWS = 8; (void)ROWS; return __VA_ARGS__; } \
+    if ((channels) == 32 && (hw) == 16) { constexpr int C = 32, HW = 16, ROWS = 8; (void)ROWS; return __VA_ARGS__; } \
+    if ((channels) == 64 && (hw) == 8) { constexpr int C = 64, HW = 8, ROWS = 8; (void)ROWS; return __VA_ARGS__; }   \
+    return (int)hipErrorInvalidValue;                                                                                 \
+  } while (0)
+
+// The tail of every launch that left P partial slabs per gradient: the caller takes the count and has them summed
+// later (sgmcmc_wrw_reduce_many, a carrier launch's riders), or each set is summed here by one wrw_reduce_kernel
+// launch, in the order given -- same kernel, same grid either way, so the route does not show in the bits.
+struct SlabSet {
+  const float* part;   // [P][E]
+  int E;
+  float* out;          // nullptr: this gradient was not asked for
+  int taps;            // sgmcmc_reduce_job.taps
+};
+inline int finish_slabs(int* deferred_slabs, int P, hipStream_t s, const SlabSet* sets, int n_sets) {
+  if (deferred_slabs) {
+    *deferred_slabs = P;
+  } else {
+    for (const SlabSet* q = sets; q != sets + n_sets; ++q)
+      if (q->out)
+        SGMCMC_LAUNCH(wrw_reduce_kernel, dim3((unsigned)reduce_blocks(P, q->E)), dim3(256), 0, s, q->part, P, q->E, q->out,
+                      q->taps);
+  }
+  return (int)hipGetLastError();
+}
+inline int finish_slabs(int* deferred_slabs, int P, hipStream_t s, std::initializer_list<SlabSet> sets) {
+  return finish_slabs(deferred_slabs, P, s, sets.begin(), (int)sets.size());
+}
+
+// sgmcmc_conv_bwd_epilogue -> BwdEpilogue, with every check any entry point makes (n_slices is the launcher's).  An
+// entry that supports only part of the epilogue adds its own refusals; wrw_mult is read by sgmcmc_conv3x3_bwd_ex alone.
+inline int epilogue_from_abi(const sgmcmc_conv_bwd_epilogue* epi, int n_img, BwdEpilogue& E) {
+  E = BwdEpilogue{};
+  if (epi->e_out && !epi->e_dout) return (int)hipErrorInvalidValue;      // (e_dout alone: added unmasked)
+  const bool sums = epi->s_partial != nullptr;
+  if (sums && (!epi->s_y || !epi->s_out || !epi->s_mean || !epi->s_invstd)) return (int)hipErrorInvalidValue;
+  if (epi->mask_dx && !sums) return (int)hipErrorInvalidValue;
+  if (epi->wrw_mult < 0 || epi->wrw_mult > 64) return (int)hipErrorInvalidValue;
+  E.e_dout = epi->e_dout; E.e_out = epi->e_out;
+  E.mask_dx = epi->mask_dx != 0;
+  E.wrw_mult = epi->wrw_mult;
+  if (sums) {
+    E.s_y = epi->s_y; E.s_out = epi->s_out; E.s_mean = epi->s_mean; E.s_invstd = epi->s_invstd;
+    E.s_partial = epi->s_partial;
+    if (epi->group_imgs < 0 || (epi->group_imgs > 0 && n_img % epi->group_imgs)) return (int)hipErrorInvalidValue;
+    set_groups(E, epi->group_imgs);
+  }
+  return 0;
+}
+
 template <int C, int HW, int ROWS>
 int launch_wrw(const float* x, const float* dy, float* dw, float* part, int n_img, hipStream_t s) {
   using G = WrwCfg<C, HW, ROWS>;
@@ -1108,13 +1191,7 @@ int launch_bwd(const float* x, const float* w, const float* dy, float* dx, float
   else if (sums) SGMCMC_LAUNCH(k01, grid, dim3(256), lds, s, x, w, dy, dx, part, n_dgrad, n_items, Ev, R);
   else SGMCMC_LAUNCH(k00, grid, dim3(256), lds, s, x, w, dy, dx, part, n_dgrad, n_items, Ev, R);
   if (which == 1) return (int)hipGetLastError();        // no slabs were written
-  if (n_slabs) {  // the caller reduces the slabs later (sgmcmc_wrw_reduce_many)
-    *n_slabs = P;
-  } else {
-    const int E = C * C * 9;
-    SGMCMC_LAUNCH(wrw_reduce_kernel, dim3((unsigned)reduce_blocks(P, E)), dim3(256), 0, s, part, P, E, dw, 9);
-  }
-  return (int)hipGetLastError();
+  return finish_slabs(n_slabs, P, s, {{part, C * C * 9, dw, 9}});
 }
 
 }  // namespace conv
@@ -1126,21 +1203,14 @@ extern "C" int sgmcmc_conv3x3_bwd(const float* x, const float* w, const float* d
   SGMCMC_FRESH_ERROR_STATE();
   if (!x || !w || !dy || !dx || !scratch || n_img <= 0 || (!dw && !deferred_slabs))
     return (int)hipErrorInvalidValue;
-  hipStream_t s = (hipStream_t)stream;
-  int* d = deferred_slabs;
-  if (channels == 16 && hw == 32) return conv::launch_bwd<16, 32, 8>(x, w, dy, dx, dw, scratch, n_img, d, s);
-  if (channels == 32 && hw == 16) return conv::launch_bwd<32, 16, 8>(x, w, dy, dx, dw, scratch, n_img, d, s);
-  if (channels == 64 && hw == 8) return conv::launch_bwd<64, 8, 8>(x, w, dy, dx, dw, scratch, n_img, d, s);
-  return (int)hipErrorInvalidValue;
+  SGMCMC_FOR_TRUNK_SHAPE(channels, hw, conv::launch_bwd<C, HW, ROWS>(x, w, dy, dx, dw, scratch, n_img, deferred_slabs,
+                                                                     (hipStream_t)stream));
 }
 
 static int conv3x3_bwd_with(const float* x, const float* w, const float* dy, float* dx, float* dw, float* scratch,
                             int n_img, int channels, int hw, int* d, hipStream_t s, const conv::BwdEpilogue& E,
                             int which = 0, const conv::RideJobs& R = conv::RideJobs{}) {
-  if (channels == 16 && hw == 32) return conv::launch_bwd<16, 32, 8>(x, w, dy, dx, dw, scratch, n_img, d, s, E, which, R);
-  if (channels == 32 && hw == 16) return conv::launch_bwd<32, 16, 8>(x, w, dy, dx, dw, scratch, n_img, d, s, E, which, R);
-  if (channels == 64 && hw == 8) return conv::launch_bwd<64, 8, 8>(x, w, dy, dx, dw, scratch, n_img, d, s, E, which, R);
-  return (int)hipErrorInvalidValue;
+  SGMCMC_FOR_TRUNK_SHAPE(channels, hw, conv::launch_bwd<C, HW, ROWS>(x, w, dy, dx, dw, scratch, n_img, d, s, E, which, R));
 }
 
 extern "C" int sgmcmc_conv3x3_bwd_add(const float* x, const float* w, const float* dy, float* dx, const float* e_dout,
@@ -1159,21 +1229,8 @@ static int conv3x3_bwd_ex_with(const float* x, const float* w, const float* dy, 
                                int hw, int* deferred_slabs, void* stream, const conv::RideJobs& R) {
   if (!x || !w || !dy || !dx || !epi || !scratch || n_img <= 0 || (!dw && !deferred_slabs))
     return (int)hipErrorInvalidValue;
-  if (epi->e_out && !epi->e_dout) return (int)hipErrorInvalidValue;      // (e_dout alone: added unmasked)
-  const bool sums = epi->s_partial != nullptr;
-  if (sums && (!epi->s_y || !epi->s_out || !epi->s_mean || !epi->s_invstd)) return (int)hipErrorInvalidValue;
-  if (epi->mask_dx && !sums) return (int)hipErrorInvalidValue;
-  conv::BwdEpilogue E{};
-  E.e_dout = epi->e_dout; E.e_out = epi->e_out;
-  E.mask_dx = epi->mask_dx != 0;
-  if (epi->wrw_mult < 0 || epi->wrw_mult > 64) return (int)hipErrorInvalidValue;
-  E.wrw_mult = epi->wrw_mult;
-  if (sums) {
-    E.s_y = epi->s_y; E.s_out = epi->s_out; E.s_mean = epi->s_mean; E.s_invstd = epi->s_invstd;
-    E.s_partial = epi->s_partial;
-    if (epi->group_imgs < 0 || (epi->group_imgs > 0 && n_img % epi->group_imgs)) return (int)hipErrorInvalidValue;
-    conv::set_groups(E, epi->group_imgs);
-  }
+  conv::BwdEpilogue E;
+  if (const int bad = conv::epilogue_from_abi(epi, n_img, E)) return bad;
   return conv3x3_bwd_with(x, w, dy, dx, dw, scratch, n_img, channels, hw, deferred_slabs, (hipStream_t)stream, E, 0, R);
 }
 
@@ -1235,8 +1292,7 @@ extern "C" int sgmcmc_wrw_reduce_many(const sgmcmc_reduce_job* jobs, int n_jobs,
 
 extern "C" int64_t sgmcmc_conv3x3_wrw_scratch_floats(int n_img, int channels, int hw) {
   const int rows = 8;
-  if (!((channels == 16 && hw == 32) || (channels == 32 && hw == 16) || (channels == 64 && hw == 8)) || n_img <= 0)
-    return -1;
+  if (!conv::is_trunk_shape(channels, hw) || n_img <= 0) return -1;
   const int n_items = n_img * (hw / rows);
   const int per = channels >= 64 ? 4 : 2;   // items per slab (WrwCfg::ITEMS)
   return (int64_t)((n_items + per - 1) / per) * channels * channels * 9;
@@ -1246,17 +1302,12 @@ extern "C" int sgmcmc_conv3x3_wrw(const float* x, const float* dy, float* dw, fl
                                   int channels, int hw, void* stream) {
   SGMCMC_FRESH_ERROR_STATE();
   if (!x || !dy || !dw || !scratch || n_img <= 0) return (int)hipErrorInvalidValue;
-  hipStream_t s = (hipStream_t)stream;
-  if (channels == 16 && hw == 32) return conv::launch_wrw<16, 32, 8>(x, dy, dw, scratch, n_img, s);
-  if (channels == 32 && hw == 16) return conv::launch_wrw<32, 16, 8>(x, dy, dw, scratch, n_img, s);
-  if (channels == 64 && hw == 8) return conv::launch_wrw<64, 8, 8>(x, dy, dw, scratch, n_img, s);
-  return (int)hipErrorInvalidValue;
+  SGMCMC_FOR_TRUNK_SHAPE(channels, hw, conv::launch_wrw<C, HW, ROWS>(x, dy, dw, scratch, n_img, (hipStream_t)stream));
 }
 
 extern "C" int sgmcmc_conv3x3_stat_slices(int n_img, int channels, int hw) {
   SGMCMC_FRESH_ERROR_STATE();
-  if (!((channels == 16 && hw == 32) || (channels == 32 && hw == 16) || (channels == 64 && hw == 8)) || n_img <= 0)
-    return -1;
+  if (!conv::is_trunk_shape(channels, hw) || n_img <= 0) return -1;
   return n_img * (hw / 8);
 }
 
@@ -1268,10 +1319,7 @@ extern "C" int sgmcmc_conv3x3_bn_eval(const float* x, const float* w, const floa
   if (!x || !w || !gamma || !beta || !running_mean || !running_var || !y || n_img <= 0) return (int)hipErrorInvalidValue;
   const conv::EvalBn V = {gamma, beta, running_mean, running_var, residual, (float)eps, relu};
   hipStream_t s = (hipStream_t)stream;
-  if (channels == 16 && hw == 32) return conv::launch_conv3x3_eval<16, 32, 8>(x, w, y, n_img, V, s);
-  if (channels == 32 && hw == 16) return conv::launch_conv3x3_eval<32, 16, 8>(x, w, y, n_img, V, s);
-  if (channels == 64 && hw == 8) return conv::launch_conv3x3_eval<64, 8, 8>(x, w, y, n_img, V, s);
-  return (int)hipErrorInvalidValue;
+  SGMCMC_FOR_TRUNK_SHAPE(channels, hw, conv::launch_conv3x3_eval<C, HW, ROWS>(x, w, y, n_img, V, s));
 }
 
 extern "C" int sgmcmc_conv3x3(const float* x, const float* w, float* y, int n_img, int channels, int hw,
@@ -1280,8 +1328,5 @@ extern "C" int sgmcmc_conv3x3(const float* x, const float* w, float* y, int n_im
   if (!x || !w || !y || n_img <= 0 || (stats && transpose_w)) return (int)hipErrorInvalidValue;
   hipStream_t s = (hipStream_t)stream;
   const bool t = transpose_w != 0;
-  if (channels == 16 && hw == 32) return conv::launch_conv3x3<16, 32, 8>(x, w, y, n_img, t, stats, s);
-  if (channels == 32 && hw == 16) return conv::launch_conv3x3<32, 16, 8>(x, w, y, n_img, t, stats, s);
-  if (channels == 64 && hw == 8) return conv::launch_conv3x3<64, 8, 8>(x, w, y, n_img, t, stats, s);
-  return (int)hipErrorInvalidValue;  // the caller keeps such shapes on the library path
+  SGMCMC_FOR_TRUNK_SHAPE(channels, hw, conv::launch_conv3x3<C, HW, ROWS>(x, w, y, n_img, t, stats, s));
 }

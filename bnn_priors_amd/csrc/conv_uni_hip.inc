@@ -450,12 +450,8 @@ extern "C" int sgmcmc_conv3x3_bwd_uniform(const float* x, const float* w, const 
   if (!x || !w || !dy || !dx || !scratch || n_img <= 0) return (int)hipErrorInvalidValue;
   conv::BwdEpilogue E{};
   if (epi) {
-    if (epi->e_out && !epi->e_dout) return (int)hipErrorInvalidValue;
-    const bool sums = epi->s_partial != nullptr;
-    if (sums && (!epi->s_y || !epi->s_out || !epi->s_mean || !epi->s_invstd)) return (int)hipErrorInvalidValue;
-    if ((epi->mask_dx && !sums) || epi->wrw_mult > 1 || epi->group_imgs != 0) return (int)hipErrorInvalidValue;
-    E.e_dout = epi->e_dout; E.e_out = epi->e_out; E.mask_dx = epi->mask_dx != 0;
-    if (sums) { E.s_y = epi->s_y; E.s_out = epi->s_out; E.s_mean = epi->s_mean; E.s_invstd = epi->s_invstd; E.s_partial = epi->s_partial; }
+    if (epi->wrw_mult > 1 || epi->group_imgs != 0) return (int)hipErrorInvalidValue;      // (no groups on this route)
+    if (const int bad = conv::epilogue_from_abi(epi, n_img, E)) return bad;
   }
   hipStream_t s = (hipStream_t)stream;
   if (channels == 16 && hw == 32) return convu::launch<16, 32>(x, w, dy, dx, scratch, n_img, s, E);

@@ -41,12 +41,8 @@ __global__ __launch_bounds__(kT) void fwd_kernel(const float* __restrict__ x, co
     const float* __restrict__ src = x + (((size_t)n * g.C + c) * g.H + 2 * oi) * g.W + 2 * oj;
     const float2 r0 = *reinterpret_cast<const float2*>(src);
     const float2 r1 = *reinterpret_cast<const float2*>(src + g.W);
-    float m = r0.x;     // NaNs propagate as in ATen's max_pool2d / relu
-    if (r0.y > m || r0.y != r0.y) m = r0.y;
-    if (r1.x > m || r1.x != r1.x) m = r1.x;
-    if (r1.y > m || r1.y != r1.y) m = r1.y;
-    const float t = m + b;
-    y[((size_t)n * g.C + c) * PO + p] = t > 0.f ? t : (t != t ? t : 0.f);
+    int code;
+    y[((size_t)n * g.C + c) * PO + p] = conv::pool_window(r0, r1, b, &code);
   }
 }
 
@@ -63,16 +59,9 @@ __global__ __launch_bounds__(kT) void bwd_kernel(const float* __restrict__ x, co
     const size_t off = (((size_t)n * g.C + c) * g.H + 2 * oi) * g.W + 2 * oj;
     const float2 r0 = *reinterpret_cast<const float2*>(x + off);
     const float2 r1 = *reinterpret_cast<const float2*>(x + off + g.W);
-    // first maximum in scan order (0,0), (0,1), (1,0), (1,1): strict comparisons
-    float m = r0.x;
-    int k = 0;
-    if (r0.y > m || r0.y != r0.y) { m = r0.y; k = 1; }
-    if (r1.x > m || r1.x != r1.x) { m = r1.x; k = 2; }
-    if (r1.y > m || r1.y != r1.y) { m = r1.y; k = 3; }
-    const float d = (m + b > 0.f) ? dy[((size_t)n * g.C + c) * PO + p] : 0.f;
-    acc += d;
-    *reinterpret_cast<float2*>(dx + off) = make_float2(k == 0 ? d : 0.f, k == 1 ? d : 0.f);
-    *reinterpret_cast<float2*>(dx + off + g.W) = make_float2(k == 2 ? d : 0.f, k == 3 ? d : 0.f);
+    int code;      // (recomputed from x: this operator keeps no byte)
+    conv::pool_window(r0, r1, b, &code);
+    acc += conv::unpool_window(dx + off, g.W, dy[((size_t)n * g.C + c) * PO + p], code);
   }
   if (dbias_part) {
     __shared__ float sh[kT / 64];

@@ -39,7 +39,6 @@ class _BiasReluPool(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dy):
-        import ctypes
         lib = _hip.lib()
         x, bias = ctx.saved_tensors
         dy = dy.contiguous()
@@ -58,17 +57,8 @@ class _BiasReluPool(torch.autograd.Function):
             _hip.check(err, "sgmcmc_bias_relu_pool_bwd")
         if not want_b:
             return dx, None
-        if _conv._may_defer(bias):
-            # summed with the convolutions' weight-gradient slabs at the end of the backward pass
-            torch.autograd.Variable._execution_engine.queue_callback(_conv._flush_pending)
-            _conv._pending.append((part, db, part.shape[0], 1))
-            return dx, db.view(db.shape)
-        job = (_hip.ReduceJob * 1)()
-        job[0].part, job[0].out, job[0].n_slabs, job[0].numel = part.data_ptr(), db.data_ptr(), part.shape[0], c
-        err = lib.sgmcmc_wrw_reduce_many(ctypes.cast(job, ctypes.c_void_p), 1, _conv._stream())
-        if err:
-            _hip.check(err, "sgmcmc_wrw_reduce_many")
-        return dx, db
+        # summed now, or with the convolutions' weight-gradient slabs at the end of the backward pass
+        return dx, _conv.reduce_or_defer(part, db, part.shape[0], 1, bias)
 
 
 def bias_relu_pool(x, bias=None):
@@ -86,19 +76,9 @@ def head_supported(h, weight, bias):
             and weight.dtype == torch.float32 and (bias is None or bias.shape == (weight.shape[0],)))
 
 
-def _reduce_rows(slabs, out, defer):
-    "out <- sum over rows of slabs [n][numel]: with the pass's other slabs if nothing reads `out` before"
-    import ctypes
-    if defer:
-        torch.autograd.Variable._execution_engine.queue_callback(_conv._flush_pending)
-        _conv._pending.append((slabs, out, slabs.shape[0], 1))
-        return out.view(out.shape)
-    job = (_hip.ReduceJob * 1)()
-    job[0].part, job[0].out, job[0].n_slabs, job[0].numel = slabs.data_ptr(), out.data_ptr(), slabs.shape[0], out.numel()
-    err = _hip.lib().sgmcmc_wrw_reduce_many(ctypes.cast(job, ctypes.c_void_p), 1, _conv._stream())
-    if err:
-        _hip.check(err, "sgmcmc_wrw_reduce_many")
-    return out
+def _reduce_rows(slabs, param):
+    "the gradient of ``param`` <- sum over rows of slabs [n][numel]: with the pass's other slabs if nothing reads it before"
+    return _conv.reduce_or_defer(slabs, torch.empty_like(param), slabs.shape[0], 1, param)
 
 
 # ---- head + loss + both backward passes in one launch (csrc/pool_hip.inc, head::loss_kernel) ----------------------
@@ -211,8 +191,8 @@ class _PoolLinear(torch.autograd.Function):
             ctx.fused = None
             if partial is not None:
                 _bnlink.tag_gradient(dh, partial, ctx.h_shape[0])
-            dw = _reduce_rows(sw, torch.empty_like(weight), _conv._may_defer(weight)) if sw is not None else None
-            db = _reduce_rows(sb, torch.empty_like(bias), _conv._may_defer(bias)) if sb is not None else None
+            dw = _reduce_rows(sw, weight) if sw is not None else None
+            db = _reduce_rows(sb, bias) if sb is not None else None
             return dh, dw, db, None, None, None
         ctx.fused = None
         dlogits = dlogits.contiguous()
@@ -239,9 +219,9 @@ class _PoolLinear(torch.autograd.Function):
             _hip.check(err, "sgmcmc_pool_linear_bwd")
         dw = db = None
         if want_w:
-            dw = _reduce_rows(sw, torch.empty_like(weight), _conv._may_defer(weight))
+            dw = _reduce_rows(sw, weight)
         if want_b:
-            db = _reduce_rows(sb, torch.empty_like(bias), _conv._may_defer(bias))
+            db = _reduce_rows(sb, bias)
         return dh, dw, db, None, None, None
 
 
@@ -327,7 +307,7 @@ class _Linear(torch.autograd.Function):
             _hip.check(err, "sgmcmc_linear_bwd")
         dw = None
         if slabs is not None:     # the row groups' slabs: summed with the pass's other slabs when nothing reads dw earlier
-            dw = _reduce_rows(slabs.view(slabs.shape[0], -1), torch.empty_like(weight), _conv._may_defer(weight))
+            dw = _reduce_rows(slabs.view(slabs.shape[0], -1), weight)
         return dx, dw, db, None
 
 

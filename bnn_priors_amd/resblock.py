@@ -133,18 +133,9 @@ def _conv_bn_conv_fwd(lib, x, w1, g1, b1, rm1, rv1, mom1, eps1, w2, s):
     return y1, h, saved1, y2, stats2, slices
 
 
-def _reduce_or_defer(lib, w, part, n_slabs, s):
-    dw = torch.empty_like(w)
-    if _conv._may_defer(w):      # summed with the pass's other slabs by ONE launch at its end
-        torch.autograd.Variable._execution_engine.queue_callback(_conv._flush_pending)
-        _conv._pending.append((part, dw, n_slabs, 9))
-        return dw.view(dw.shape)
-    job = (_hip.ReduceJob * 1)()
-    job[0].part, job[0].out, job[0].n_slabs, job[0].numel, job[0].taps = part.data_ptr(), dw.data_ptr(), n_slabs, dw.numel(), 9
-    err = lib.sgmcmc_wrw_reduce_many(ctypes.cast(job, ctypes.c_void_p), 1, s)
-    if err:
-        _hip.check(err, "sgmcmc_wrw_reduce_many")
-    return dw
+def _reduce_or_defer(w, part, n_slabs):
+    "dw <- the sum of a trunk launch's slabs: now, or with the pass's other slabs by ONE launch at its end"
+    return _conv.reduce_or_defer(part, torch.empty_like(w), n_slabs, 9, w)
 
 
 def _conv_bn_bwd_two_launch(lib, x, w, y, out, dout, saved, g, dgb, e_dout, e_out, s):
@@ -169,7 +160,7 @@ def _conv_bn_bwd_two_launch(lib, x, w, y, out, dout, saved, g, dgb, e_dout, e_ou
                                          e_out.data_ptr(), 0, part.data_ptr(), n, c, hw, ctypes.byref(slabs), s)
     if err:
         _hip.check(err, "sgmcmc_conv3x3_bwd")
-    return dx, _reduce_or_defer(lib, w, part, slabs.value, s)
+    return dx, _reduce_or_defer(w, part, slabs.value)
 
 
 def _conv_bn_bwd(lib, x, w, y, out, dout, saved, g, dgb, e_dout, e_out, s):
@@ -193,7 +184,7 @@ def _conv_bn_bwd(lib, x, w, y, out, dout, saved, g, dgb, e_dout, e_out, s):
                                     hw, ctypes.byref(slabs), s)
     if err:
         _hip.check(err, "sgmcmc_conv3x3_bn_bwd")
-    return dx, _reduce_or_defer(lib, w, part, slabs.value, s)
+    return dx, _reduce_or_defer(w, part, slabs.value)
 
 
 def _bn_dx(lib, dout, out, y, saved, g, dgb, partial, n_partials, s, G=1, masked=False):
@@ -219,43 +210,6 @@ def _bn_sums(lib, dout, out, y, saved, s, G=1):
     if err:
         _hip.check(err, "sgmcmc_bn_bwd_sums")
     return sums, n_sums.value
-
-
-def _conv_bwd_ex(lib, x, w, dy, s, add=None, sums_for=None, G=1):
-    """both gradients of y = conv3x3(x, w) given dy; ``add`` = (e_dout, e_out): dx += e_dout * [e_out > 0] (e_out None:
-    e_dout is masked already); ``sums_for`` = (y_bn, out_bn, saved_bn): also the partial sums of the BatchNorm backward
-    whose incoming gradient dx is, and (bnlink.PREMASK) dx is stored as dx * [out_bn > 0]
-    -> (dx, dw, partial or None, n_partials)"""
-    n, c, hw = x.shape[0], x.shape[1], x.shape[2]
-    if _conv.persistent_bwd(c, hw) and not (_conv.SIDE_STREAM and _conv._may_defer(w)):
-        defer = _conv._may_defer(w)
-        if defer:      # summed with the pass's other slabs by ONE launch at its end
-            torch.autograd.Variable._execution_engine.queue_callback(_conv._flush_pending)
-        return _conv.frag_backward(lib, x, w, dy, defer, add=add, sums_for=sums_for)
-    part = torch.empty(lib.sgmcmc_conv3x3_wrw_scratch_floats(n, c, hw), dtype=torch.float32, device=x.device)
-    dx = torch.empty_like(x)
-    E = _hip.ConvBwdEpilogue()
-    E.wrw_mult = _conv.WRW_GROUP_MULT and G       # (several minibatches: the slab count of one)
-    if add is not None:
-        E.e_dout, E.e_out = add[0].data_ptr(), _p(add[1])
-    partial, n_partials = None, lib.sgmcmc_conv3x3_stat_slices(n, c, hw)
-    if sums_for is not None:
-        y_bn, out_bn, saved_bn = sums_for
-        partial = torch.empty((c, n_partials, 2), dtype=torch.float64, device=x.device)
-        E.s_y, E.s_out, E.s_mean, E.s_invstd = y_bn.data_ptr(), out_bn.data_ptr(), saved_bn[0].data_ptr(), saved_bn[1].data_ptr()
-        E.s_partial = partial.data_ptr()
-        E.group_imgs = n // G if G > 1 else 0
-        E.mask_dx = int(_bnlink.PREMASK)
-    slabs = ctypes.c_int(0)
-    if _conv.SIDE_STREAM and _conv._may_defer(w):
-        # the weight-gradient slabs leave the critical path: side stream, joined before the pass's slab reduction
-        _conv.split_backward(lib, x, w, dy, dx, E, part, slabs)
-    else:
-        # (slab reductions pending from earlier launches of this pass ride in this one: conv.take_riders)
-        err = _conv.bwd_ex(lib, x, w, dy, dx, E, None, part, slabs, s, _conv.take_riders(c, hw))
-        if err:
-            _hip.check(err, "sgmcmc_conv3x3_bwd_ex")
-    return dx, _reduce_or_defer(lib, w, part, slabs.value, s), partial, n_partials
 
 
 class _Block(torch.autograd.Function):
@@ -304,11 +258,11 @@ class _Block(torch.autograd.Function):
             # (masked: the launch that produced dout stored it as dout * [out > 0] -- bnlink.PREMASK)
             sums2, n2, masked = up if up is not None else (*_bn_sums(lib, dout, out, y2, saved2, s, G), False)
             dy2 = _bn_dx(lib, dout, out, y2, saved2, g2, dgb[1], sums2, n2, s, G, masked)
-            dh, dw2, sums1, n1 = _conv_bwd_ex(lib, h, w2, dy2, s, sums_for=(y1, h, saved1), G=G)
+            dh, dw2, sums1, n1 = _conv.trunk_backward(lib, h, w2, dy2, s, sums_for=(y1, h, saved1), G=G)
             dy1 = _bn_dx(lib, dh, h, y1, saved1, g1, dgb[0], sums1, n1, s, G, _bnlink.PREMASK)
             # ... and this block's input came out of a BatchNorm + ReLU too: its sums ride in conv1's gradient launch
-            dx, dw1, sums0, n0 = _conv_bwd_ex(lib, x, w1, dy1, s, add=(dout, None if masked else out),
-                                              sums_for=None if src_y is None else (src_y, x, src_saved), G=G)
+            dx, dw1, sums0, n0 = _conv.trunk_backward(lib, x, w1, dy1, s, add=(dout, None if masked else out),
+                                                      sums_for=None if src_y is None else (src_y, x, src_saved), G=G)
             if sums0 is not None:
                 _bnlink.tag_gradient(dx, sums0, n0, _bnlink.PREMASK)
         elif (x.shape[1], x.shape[2]) in FUSED_BN_BWD:
