@@ -1717,3 +1717,5 @@ int sgmcmc_debug_normals(float* out, int64_t start, int64_t n, uint64_t seed, ui
 #include "diag_hip.inc"
 // ... and their rank-normalised form: normal scores of the average ranks, tail quantiles and indicators (fp64)
 #include "rank_hip.inc"
+// model comparison from the same tables: PSIS-LOO with Pareto-k and WAIC, pointwise and in total (fp64)
+#include "psis_hip.inc"

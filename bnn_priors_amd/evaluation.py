@@ -24,7 +24,7 @@ import torch
 from . import _capture
 
 __all__ = ("evaluate_model", "evaluate_ood", "predictive_tables", "logit_tables", "ensemble_across_chains",
-           "ensemble_metrics", "gather_samples")
+           "ensemble_metrics", "gather_samples", "evaluate_loo", "evaluate_marglik")
 
 
 def _labels_of(dataloader):
@@ -356,6 +356,45 @@ def evaluate_model(model, dataloader_test, samples, likelihood_eval=True, accura
         from . import calibration
         out.update(calibration.calibration_metrics(labels, calibration.ensemble_probs(acc).probs))
     return out
+
+
+def evaluate_loo(model, dataloader_train, samples, chains=None):
+    """Model comparison on the rows the chains were fitted on (model_comparison.py: PSIS-LOO and WAIC, on the device,
+    fp64): ``predictive_tables`` of ``dataloader_train``, then ``loo`` and ``waic`` of its ``lps [E, N]``.  Plain floats:
+    ``elpd_loo``, ``elpd_loo_se``, ``p_loo``, ``elpd_waic``, ``p_waic``, ``pareto_k_max`` and ``pareto_k_bad`` (how many
+    observations' Pareto-k exceed min(1 - 1 / log10(E), 0.7)).  ``chains=M``: ``samples`` hold M chains of equal length
+    one after the other (``gather_samples``' layout); the table is viewed as [M, E / M, N] and
+    ``model_comparison.relative_eff`` sets each observation's tail length.  The reference has no such function."""
+    from . import model_comparison
+    lps = predictive_tables(model, dataloader_train, samples)[0]
+    r_eff = None
+    if chains is not None:
+        M = int(chains)
+        if M < 1 or lps.shape[0] % M:
+            raise ValueError(f"{lps.shape[0]} samples do not hold {chains} chains of equal length")
+        r_eff = model_comparison.relative_eff(lps.unflatten(0, (M, lps.shape[0] // M)))
+    res, wres = model_comparison.loo_waic(lps, r_eff)
+    return {"elpd_loo": res.elpd_loo, "elpd_loo_se": res.se, "p_loo": res.p_loo, "elpd_waic": wres.elpd_waic,
+            "p_waic": wres.p_waic, "pareto_k_max": res.k_max, "pareto_k_bad": float(res.n_bad)}
+
+
+@torch.no_grad()
+def evaluate_marglik(model, train_samples, eval_samples):
+    """exp_utils.py:383-406: the model's ``log_prior()`` under every sample -- the parameters of ``train_samples``
+    overwritten by those of ``eval_samples`` -- as ``simple_logmarglik`` (their log-mean-exp), ``mean_loglik`` (their
+    mean) and ``simple_marglik`` (the mean of their exponentials), in the reference's float32.  Host-side and small."""
+    n = _n_samples(train_samples)
+    if n != _n_samples(eval_samples):
+        raise ValueError(f"{n} train samples but {_n_samples(eval_samples)} eval samples")
+    log_priors = []
+    for e in range(n):
+        model.load_state_dict({**{k: v[e] for k, v in train_samples.items()},
+                               **{k: v[e] for k, v in eval_samples.items()}})
+        log_priors.append(model.log_prior().item())
+    log_priors = torch.tensor(log_priors)
+    return {"simple_logmarglik": log_priors.logsumexp(dim=0).item() - math.log(n),
+            "mean_loglik": log_priors.mean().item(),
+            "simple_marglik": log_priors.exp().mean().item()}
 
 
 @torch.no_grad()

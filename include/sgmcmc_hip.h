@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGMCMC_ABI_VERSION 14
+#define SGMCMC_ABI_VERSION 15
 #define SGMCMC_CHUNK 4096 /* default elements per arena chunk = 256 threads x 4 items x 4 elements */
 #define SGMCMC_CHUNK_SMALL 1024 /* small models: one item per thread, 4x more workgroups */
 #define SGMCMC_NSUMS 6
@@ -998,6 +998,69 @@ int sgmcmc_chain_quantiles(const double* ostat, int chains, int draws, int split
 int sgmcmc_chain_tail_indicators(const void* x, int is_f64, int64_t chain_stride, int64_t draw_stride, int chains,
                                  int draws, int64_t quantities, int split, const double* q_lower,
                                  const double* q_upper, float* lower, float* upper, void* stream);
+
+/* ---- Model comparison: PSIS-LOO with Pareto-k and WAIC (fp64, deterministic) -------------------------------------------
+ * Vehtari, Gelman, Gabry 2017; Vehtari, Simpson, Gelman, Yao, Gabry 2024; Watanabe 2010; the generalised Pareto fit of
+ * Zhang and Stephens 2009.  The reference has no such function (its only model-comparison number is the log-mean-exp of
+ * exp_utils.evaluate_marglik); this is the definition, restated in tests/psis_reference.py.
+ * ll[s][i]: `draws` (S) x `observations` (N) values of log p(y_i | theta_s), fp32 (is_f64 = 0) or fp64, element (s, i) at
+ * table[s * draw_stride + i]; with is_ratio != 0 the table holds the log ratios r = -ll instead (the negation is exact).
+ * fp32 is widened on load, all arithmetic is fp64, every operation is rounded once (nothing is contracted into an fma).
+ * r_eff [N] (fp64, may be NULL: 1 everywhere) is the relative efficiency of the draws.
+ * Per observation (column) i, with r = -ll:
+ *  1. x_s = r_s - max_s r_s (one rounding).
+ *  2. M = ceil(min(0.2 S, 3 sqrt(S / r_eff))), at most SGMCMC_PSIS_MAX_TAIL (which binds only for S > 2720 with
+ *     r_eff < 1); cut = max(x_(S-M-1), log DBL_MIN) with x_(k) the k-th smallest counted from 0 and log DBL_MIN the
+ *     constant SGMCMC_PSIS_LOG_DBL_MIN; ec = exp(cut).
+ *  3. the tail: the draws with x_s > cut (strict, exact), n2 of them (n2 <= M), in ascending order, ties by draw index.
+ *     n2 <= 4: khat = +inf, nothing is smoothed.
+ *  4. else t_j = exp(x_tail_j) - ec, j = 0 .. n2-1; m = 30 + floor(sqrt(n2));
+ *     b_j = 1 / t_(n2-1) + (1 - sqrt(m / (j - 1/2))) / (3 t_(floor(n2/4 + 1/2) - 1)), j = 1 .. m;
+ *     kappa_j = (sum_i log1p(-b_j t_i)) / n2;  L_j = n2 (log(-b_j / kappa_j) - kappa_j - 1);
+ *     w_j = 1 / sum_l exp(L_l - L_j);  bbar = sum_j b_j w_j;  kappa = (sum_i log1p(-bbar t_i)) / n2;
+ *     sigma = -kappa / bbar;  khat = (n2 kappa + 5) / (n2 + 10).  Every sum runs over ascending index.
+ *  5. khat finite: tail element j becomes log(sigma expm1(-khat log1p(-p_j)) / khat + ec), p_j = (j + 1/2) / n2
+ *     (khat = 0: log(-sigma log1p(-p_j) + ec)).
+ *  6. x_s <- min(x_s, 0); lw_s = x_s - logsumexp_s x, logsumexp_s v = max_s v + log sum_s exp(v_s - max_s v) over
+ *     ascending s.
+ * Pointwise outputs (rows of `pointwise` [SGMCMC_PSIS_POINTWISE][N], in this order):
+ *     pareto_k = khat;  elpd_loo = logsumexp_s (lw_s + ll_s);  lppd = logsumexp_s ll_s - log S;
+ *     p_loo = lppd - elpd_loo;  p_waic = sum_s (ll_s - mean_s ll)^2 / (S - 1) (two passes);  elpd_waic = lppd - p_waic.
+ * NaN rule: a column with a non-finite ll, or whose r_eff is not a positive finite number, gives NaN in every output
+ * (M = n2 = 0); nothing else is special-cased.  A constant column has an empty tail, khat = +inf, uniform weights.
+ * Totals (`totals` [SGMCMC_PSIS_TOTALS], device memory): sum_i elpd_loo, se(elpd_loo), sum_i p_loo, sum_i lppd,
+ * sum_i elpd_waic, se(elpd_waic), sum_i p_waic, #{khat > k_threshold}, max_i khat (NaN if one is NaN), with
+ * se(v) = sqrt(N var_i(v, ddof = 1)) in two passes; every sum over i in an order fixed by N alone (256 interleaved
+ * partial sums in ascending i, then a fixed tree).  The caller passes k_threshold = min(1 - 1 / log10(S), 0.7).
+ * The caller provides every buffer; nothing is allocated, nothing synchronises, everything runs on the given stream;
+ * no atomics; the tail is found by counting, so no schedule changes a bit; a column's result depends on that column
+ * (and its r_eff) only, and the chunking changes no bit.  Limits: SGMCMC_PSIS_MIN_DRAWS <= S <= SGMCMC_PSIS_MAX_DRAWS
+ * (counts fit int32, the tail's rows uint16), N >= 1, draw_stride >= N; anything else, a NULL required pointer or a
+ * workspace too small for 64 observations (for N, if N < 64) returns hipErrorInvalidValue and launches nothing. */
+#define SGMCMC_PSIS_MIN_DRAWS 5
+#define SGMCMC_PSIS_MAX_DRAWS 32768
+#define SGMCMC_PSIS_MAX_TAIL 544   /* ceil(3 sqrt(32768)) */
+#define SGMCMC_PSIS_OWN 16         /* draws of its column that a thread of the selection kernel places */
+#define SGMCMC_PSIS_POINTWISE 6
+#define SGMCMC_PSIS_TOTALS 9
+#define SGMCMC_PSIS_LOG_DBL_MIN (-708.3964185322641) /* the double nearest log(2^-1022) */
+
+/* Bytes of workspace with which `observations` columns are one chunk: per observation 8 rows + 64 + 2 S, rows =
+ * min(ceil(0.2 S), SGMCMC_PSIS_MAX_TAIL) with r_eff, else min(that, ceil(3 sqrt(S))).  -1 for a refused shape.
+ * A chunk of W observations lies in the workspace as tail [rows][W] fp64 (row 0: the largest), record [6][W] fp64,
+ * counters [4][W] int32 and pos [S][W] uint16 (a draw's tail row, 0xffff outside the tail), in this order. */
+int64_t sgmcmc_psis_workspace_bytes(int draws, int64_t observations, int has_r_eff);
+/* Steps 1-6 and the pointwise outputs.  workspace (8-byte aligned): all N observations at once if workspace_bytes
+ * allows, else chunks of the largest multiple of 64 that fits.  Optional outputs (may be NULL): fit [2][N] fp64 (sigma,
+ * NaN without a fit; cut), counts [2][N] int32 (M; n2), lw [S][N] fp64 (contiguous).  Per chunk four launches: one
+ * thread per column streams the table (statistics, M), the selection kernel places the tail by counting (S^2 N
+ * compares), one thread per column fits (m + 1 passes of log1p over its tail), one thread per column finishes. */
+int sgmcmc_psis_loo(const void* table, int is_f64, int is_ratio, int64_t draw_stride, int draws, int64_t observations,
+                    const double* r_eff, void* workspace, int64_t workspace_bytes, double* pointwise, double* fit,
+                    int32_t* counts, double* lw, void* stream);
+/* The totals of pointwise [SGMCMC_PSIS_POINTWISE][N] as sgmcmc_psis_loo wrote it.  One launch of one workgroup. */
+int sgmcmc_psis_totals(const double* pointwise, int64_t observations, double k_threshold, double* totals,
+                       void* stream);
 
 /* Test hook: out[i] = spec normal (fp32) of noise index start+i. */
 int sgmcmc_debug_normals(float* out, int64_t start, int64_t n, uint64_t seed, uint32_t stream,
