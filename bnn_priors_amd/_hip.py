@@ -24,7 +24,7 @@ INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 SOURCES = [os.path.join(_HERE, "csrc", "sgmcmc_hip.hip")]
 SOURCE = SOURCES[0]
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 CHUNK = 4096
 CHUNK_SMALL = 1024
 NSUMS = 6
@@ -180,6 +180,7 @@ MAX_CHAINS, MLP_BATCH_MULTI = 8, 128
 DIAG_MAX_SEQ, DIAG_MAX_CHAINS, DIAG_LAG_BLOCK, DIAG_TILE = 512, 64, 32, 32
 RANK_OWN, RANK_MAX_PROBS = 16, 3
 PSIS_MIN_DRAWS, PSIS_MAX_DRAWS, PSIS_MAX_TAIL, PSIS_OWN, PSIS_POINTWISE, PSIS_TOTALS = 5, 32768, 544, 16, 6, 9
+WEIGHTS_SLICE, WEIGHTS_MAX_MODELS, WEIGHTS_STATE, WEIGHTS_NOISE_PURPOSE = 1024, 32, 72, 4
 
 EXPORTS = {
     "sgmcmc_abi_version": (ctypes.c_int, []),
@@ -363,6 +364,20 @@ EXPORTS = {
                         + [ctypes.c_void_p] * 5),
     "sgmcmc_psis_totals": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p,
                                           ctypes.c_void_p]),
+    "sgmcmc_weights_workspace_bytes": (ctypes.c_int64, [ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int]),
+    "sgmcmc_stacking_init": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
+                                            ctypes.c_double, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p,
+                                            ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    "sgmcmc_stacking_iterate": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
+                                               ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
+                                               ctypes.c_void_p, ctypes.c_void_p]),
+    "sgmcmc_mixture_lpd": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 3),
+    "sgmcmc_pseudo_bma": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
+                                         ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    "sgmcmc_bb_pseudo_bma": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
+                                            ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p,
+                                            ctypes.c_int64] + [ctypes.c_void_p] * 4),
     "sgmcmc_debug_normals": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                             ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64,
                                             ctypes.c_uint32, ctypes.c_void_p]),

@@ -1719,3 +1719,5 @@ int sgmcmc_debug_normals(float* out, int64_t start, int64_t n, uint64_t seed, ui
 #include "rank_hip.inc"
 // model comparison from the same tables: PSIS-LOO with Pareto-k and WAIC, pointwise and in total (fp64)
 #include "psis_hip.inc"
+// model-averaging weights from the pointwise elpd rows: stacking, pseudo-BMA, pseudo-BMA+ and mixture densities (fp64)
+#include "weights_hip.inc"

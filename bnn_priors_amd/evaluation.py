@@ -379,6 +379,33 @@ def evaluate_loo(model, dataloader_train, samples, chains=None):
 
 
 @torch.no_grad()
+def evaluate_model_average(fits, dataloader_train, dataloader_test, method="stacking"):
+    """Model averaging over several fits (model_comparison.py: stacking, pseudo-BMA or pseudo-BMA+ weights, on the
+    device, fp64).  ``fits = {name: (model, samples)}``.  The weights come from the pointwise PSIS-LOO densities of
+    ``dataloader_train``'s rows (what ``evaluate_loo`` sums); the score is on ``dataloader_test``: each model's pointwise
+    lppd there (the log-mean-exp of ``predictive_tables``' ``lps`` over the samples) and ``mixture_lpd`` of those rows.
+    -> ``weights`` {name: float}, ``lpd_average`` (the weighted mixture's test log density), ``best_single`` and
+    ``lpd_best_single`` (the model with the largest test log density on its own) and ``lpd_uniform`` (equal weights).
+    The reference has no such function."""
+    from . import model_comparison
+    if not isinstance(fits, dict) or not fits:
+        raise ValueError("fits must be a non-empty dict {name: (model, samples)}")
+    results, test = {}, {}
+    for name, (model, samples) in fits.items():
+        results[name] = model_comparison.loo(predictive_tables(model, dataloader_train, samples)[0])
+        test[name] = _log_mean_exp(predictive_tables(model, dataloader_test, samples)[0], 0)
+    weights = model_comparison.model_weights(results, method)
+    names = list(weights)
+    P = torch.stack([test[n] for n in names])
+    K = len(names)
+    single = P.sum(1).cpu().tolist()
+    best = max(range(K), key=lambda k: -math.inf if math.isnan(single[k]) else single[k])
+    return {"weights": weights, "lpd_average": model_comparison.mixture_lpd(P, [weights[n] for n in names])[0],
+            "best_single": names[best], "lpd_best_single": single[best],
+            "lpd_uniform": model_comparison.mixture_lpd(P, [1.0 / K] * K)[0]}
+
+
+@torch.no_grad()
 def evaluate_marglik(model, train_samples, eval_samples):
     """exp_utils.py:383-406: the model's ``log_prior()`` under every sample -- the parameters of ``train_samples``
     overwritten by those of ``eval_samples`` -- as ``simple_logmarglik`` (their log-mean-exp), ``mean_loglik`` (their

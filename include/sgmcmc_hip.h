@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGMCMC_ABI_VERSION 15
+#define SGMCMC_ABI_VERSION 16
 #define SGMCMC_CHUNK 4096 /* default elements per arena chunk = 256 threads x 4 items x 4 elements */
 #define SGMCMC_CHUNK_SMALL 1024 /* small models: one item per thread, 4x more workgroups */
 #define SGMCMC_NSUMS 6
@@ -1061,6 +1061,73 @@ int sgmcmc_psis_loo(const void* table, int is_f64, int is_ratio, int64_t draw_st
 /* The totals of pointwise [SGMCMC_PSIS_POINTWISE][N] as sgmcmc_psis_loo wrote it.  One launch of one workgroup. */
 int sgmcmc_psis_totals(const double* pointwise, int64_t observations, double k_threshold, double* totals,
                        void* stream);
+
+/* ---- Model averaging: stacking, pseudo-BMA and pseudo-BMA+ weights (fp64, deterministic) ------------------------------
+ * Yao, Vehtari, Simpson, Gelman 2018.  The reference has no such function; this is the definition, restated in
+ * tests/weights_reference.py.  P[k][i]: `models` (K) x `observations` (N) pointwise elpd values (sgmcmc_psis_loo's
+ * elpd_loo row of each model, or any other pointwise log density), fp64, element (k, i) at P[k * model_stride + i], read
+ * in place.  All arithmetic is fp64 and every operation is rounded once (nothing is contracted into an fma).
+ * Sums over i: the observations are cut into slices of SGMCMC_WEIGHTS_SLICE = 1,024; a slice's sum is 256 partial sums
+ * and the fixed tree (partial t += partial t + 128, then t + 64, ..., t + 1); the slices are added in ascending order.
+ * Partial t of a slice holds, added in ascending order, elements t, t + 256, t + 512, t + 768 of the slice (stacking,
+ * mixture, pseudo-BMA) or elements 4t .. 4t + 3 (the bootstrap, whose thread owns one Philox counter = four
+ * observations).  Elements past N count as 0.  Sums over k and over slices start from 0 and ascend.  No atomics.
+ *  1. Pseudo-BMA: elpd_k = sum_i P[k][i];  w_k = exp(elpd_k - max_j elpd_j) / sum_j exp(elpd_j - max_j elpd_j).
+ *  2. Pseudo-BMA+ (Bayesian bootstrap), replicate b = 0 .. B-1: g_{b,i} = -log(u_{b,i}) in fp64, where u_{b,i} is the
+ *     uniform (2 (x >> 9) + 1) 2^-24 (never 0) of word i & 3 of Philox4x32-10 with the 64-bit seed as key and the counter
+ *     (quad_lo, quad_hi, b_lo, purpose << 28 | (stream & 0xfff) << 16 | b_hi16), quad = i >> 2, purpose =
+ *     SGMCMC_WEIGHTS_NOISE_PURPOSE.  z_{b,k} = (N * sum_i g_{b,i} P[k][i]) / sum_i g_{b,i};  w_{b,.} = softmax_k z_{b,.}
+ *     as in 1.  weights_k = (sum_b w_{b,k}) / B;  se_k = sqrt(sum_b (z_{b,k} - mean_b z_{.,k})^2 / (B - 1)), two passes
+ *     (NaN for B = 1); the sums over b are 256 interleaved partial sums in ascending b, then the same tree.  Row b
+ *     depends on (seed, stream, b) only: not on B, not on the workspace, not on the grid.
+ *  3. Stacking: maximise f(w) = (1/N) sum_i log sum_k w_k exp(P[k][i]) over the simplex by the EM update of mixture
+ *     proportions, from w = 1/K.  m_i = max_k P[k][i];  q_{k,i} = exp(P[k][i] - m_i);  one iteration is
+ *         mix_i = sum_k w_k q_{k,i};  r_k = (sum_i q_{k,i} / mix_i) / N;  gap = max_k r_k - 1;
+ *         lpd = sum_i (m_i + log mix_i);  then w_k <- w_k r_k.
+ *     Because f is concave and sum_k w_k r_k = 1, f(w*) - f(w) <= gap at every iterate: gap is a certificate.  The
+ *     iteration stops at the first iterate with gap <= tol, before its update is applied (converged), or when max_iter
+ *     updates have been applied; r, gap and lpd are those of the returned w.  K = 1: w = 1, gap = 0, no update.
+ *  4. Mixture log density for a given w: pointwise_i = m_i + log sum_k w_k q_{k,i};  total = sum_i pointwise_i.
+ * NaN rule: a non-finite entry anywhere in P makes every output of 1-3 NaN (every weight depends on every observation)
+ * and ends the stacking iteration (not converged); in 4 it makes that observation's pointwise value and the total NaN.
+ * Nothing else is special-cased.
+ * State record of a stacking run, `state` [SGMCMC_WEIGHTS_STATE] fp64 in device memory: updates applied, converged
+ * (0 / 1), frozen (0 / 1), gap, lpd, tol, max_iter, reserved, w [32], r [32].
+ * The caller provides every buffer; nothing is allocated, nothing synchronises, everything runs on the given stream.
+ * Limits: 1 <= K <= SGMCMC_WEIGHTS_MAX_MODELS, N >= 1, model_stride >= N; anything else, a NULL pointer, a workspace
+ * that is not 8-byte aligned or too small returns hipErrorInvalidValue and launches nothing. */
+#define SGMCMC_WEIGHTS_SLICE 1024
+#define SGMCMC_WEIGHTS_MAX_MODELS 32
+#define SGMCMC_WEIGHTS_STATE 72
+#define SGMCMC_WEIGHTS_NOISE_PURPOSE 4u /* 0-2 the sampler's, 3 augmentation's: the bootstrap shares words with none */
+
+/* Bytes of workspace: the larger of 8 slices (K + 1) (+ 8 (K + 1) N with cache_q: m and q formed once) for stacking,
+ * mixture and pseudo-BMA, and replicates * 8 slices (K + 1) for that many bootstrap replicates in one launch;
+ * slices = ceil(N / 1024).  -1 for a refused shape or a size beyond int64. */
+int64_t sgmcmc_weights_workspace_bytes(int models, int64_t observations, int64_t replicates, int cache_q);
+/* Writes the state record (w = 1/K, tol >= 0, 0 <= max_iter <= 2^52) and, with cache_q != 0, m [N] and q [K][N] into the
+ * workspace behind the partial sums.  One launch. */
+int sgmcmc_stacking_init(const double* P, int64_t model_stride, int models, int64_t observations, double tol,
+                         int64_t max_iter, int cache_q, void* workspace, int64_t workspace_bytes, double* state,
+                         void* stream);
+/* Enqueues `iters` iterations, two launches each: one workgroup per slice writes part [slices][K + 1] (sum q / mix per
+ * model, sum (m + log mix)); one workgroup adds the slices, writes r, gap, lpd and applies the update.  A frozen state
+ * (converged, max_iter reached, non-finite input) turns both into no-ops, so the result does not depend on how the
+ * iterations are batched; max_iter + 1 iterations always freeze it.  Same P, workspace and cache_q as the init call. */
+int sgmcmc_stacking_iterate(const double* P, int64_t model_stride, int models, int64_t observations, int cache_q,
+                            int iters, void* workspace, int64_t workspace_bytes, double* state, void* stream);
+/* Definition 4: w [K] in device memory -> pointwise [N] and total [1].  Two launches. */
+int sgmcmc_mixture_lpd(const double* P, int64_t model_stride, int models, int64_t observations, const double* w,
+                       void* workspace, int64_t workspace_bytes, double* pointwise, double* total, void* stream);
+/* Definition 1: out [2][K] = the weights, then elpd_k.  Two launches. */
+int sgmcmc_pseudo_bma(const double* P, int64_t model_stride, int models, int64_t observations, void* workspace,
+                      int64_t workspace_bytes, double* out, void* stream);
+/* Definition 2: z, w [B][K] (every row is written) and out [2][K] = weights, then se.  The replicates are walked in
+ * chunks of as many as the workspace holds (at least one, at most 65,535): per chunk one launch of slices x chunk
+ * workgroups and one of a thread per replicate; then one workgroup for the means and variances. */
+int sgmcmc_bb_pseudo_bma(const double* P, int64_t model_stride, int models, int64_t observations, int64_t replicates,
+                         uint64_t seed, uint32_t noise_stream, void* workspace, int64_t workspace_bytes, double* z,
+                         double* w, double* out, void* stream);
 
 /* Test hook: out[i] = spec normal (fp32) of noise index start+i. */
 int sgmcmc_debug_normals(float* out, int64_t start, int64_t n, uint64_t seed, uint32_t stream,
