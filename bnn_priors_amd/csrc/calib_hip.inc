@@ -43,6 +43,54 @@ __device__ __forceinline__ double lse_term(double x, double m) {
   return m == -INFINITY ? (x != x ? x : 0.0) : exp(x - m);
 }
 
+// The running log-sum-exp over the samples of one (row, class) entry, (m, s) with sum_e exp(x_e) = s exp(m): four
+// samples at a time, then one at a time, then the log-mean.  ensemble_kernel and uncert::rows_kernel (uncert_hip.inc)
+// both run exactly this sequence, which is what makes their probabilities the same bits.
+// (f: the factor s took when the maximum moved, 1 otherwise; t[i]: the term exp(x_i - m) that was added -- for a caller
+// that carries a second sum on the same maximum)
+__device__ __forceinline__ void lse_add4(double& m, double& s, double x0, double x1, double x2, double x3, double& f,
+                                         double* t) {
+  const double mx = fmax(fmax(m, fmax(x0, x1)), fmax(x2, x3));
+  f = 1.0;
+  if (mx > m) {
+    if (m != -INFINITY) { f = exp(m - mx); s = s * f; }
+    m = mx;
+  }
+  t[0] = lse_term(x0, m); t[1] = lse_term(x1, m); t[2] = lse_term(x2, m); t[3] = lse_term(x3, m);
+  s = (((s + t[0]) + t[1]) + t[2]) + t[3];
+}
+
+__device__ __forceinline__ void lse_add1(double& m, double& s, double x, double& f, double& t) {
+  f = 1.0;
+  if (x > m) {
+    if (m != -INFINITY) { f = exp(m - x); s = s * f; }
+    m = x;
+  }
+  t = lse_term(x, m);
+  s += t;
+}
+
+__device__ __forceinline__ void lse_add4(double& m, double& s, double x0, double x1, double x2, double x3) {
+  double f, t[4];
+  lse_add4(m, s, x0, x1, x2, x3, f, t);
+}
+
+__device__ __forceinline__ void lse_add1(double& m, double& s, double x) {
+  double f, t;
+  lse_add1(m, s, x, f, t);
+}
+
+__device__ __forceinline__ double lse_log_mean(double m, double s, int E) { return (m + log(s)) - log((double)E); }
+
+// softmax of the C log-means in l (LDS), in place and to p (global): the ensemble's probabilities of one row
+__device__ __forceinline__ void row_softmax(double* l, int C, double* __restrict__ p) {
+  double mx = l[0];
+  for (int k = 1; k < C; ++k) mx = fmax(mx, l[k]);
+  double s = 0.0;
+  for (int k = 0; k < C; ++k) { l[k] = exp(l[k] - mx); s += l[k]; }
+  for (int k = 0; k < C; ++k) { l[k] = l[k] / s; p[k] = l[k]; }
+}
+
 __global__ __launch_bounds__(256) void ensemble_kernel(const double* __restrict__ acc, const int64_t* __restrict__ labels,
                                                        int E, int N, int C, double* __restrict__ probs,
                                                        double* __restrict__ conf, int64_t* __restrict__ pred,
@@ -56,30 +104,17 @@ __global__ __launch_bounds__(256) void ensemble_kernel(const double* __restrict_
     const double* __restrict__ a = acc + (size_t)(n0 + r) * C + c;
     double m = -INFINITY, s = 0.0;
     int e = 0;
-    for (; e + 4 <= E; e += 4) {
-      const double x0 = a[(size_t)e * plane], x1 = a[(size_t)(e + 1) * plane];
-      const double x2 = a[(size_t)(e + 2) * plane], x3 = a[(size_t)(e + 3) * plane];
-      const double mx = fmax(fmax(m, fmax(x0, x1)), fmax(x2, x3));
-      if (mx > m) { s = m == -INFINITY ? s : s * exp(m - mx); m = mx; }
-      s = (((s + lse_term(x0, m)) + lse_term(x1, m)) + lse_term(x2, m)) + lse_term(x3, m);
-    }
-    for (; e < E; ++e) {
-      const double x = a[(size_t)e * plane];
-      if (x > m) { s = m == -INFINITY ? s : s * exp(m - x); m = x; }
-      s += lse_term(x, m);
-    }
-    row[t] = (m + log(s)) - log((double)E);
+    for (; e + 4 <= E; e += 4)
+      lse_add4(m, s, a[(size_t)e * plane], a[(size_t)(e + 1) * plane], a[(size_t)(e + 2) * plane],
+               a[(size_t)(e + 3) * plane]);
+    for (; e < E; ++e) lse_add1(m, s, a[(size_t)e * plane]);
+    row[t] = lse_log_mean(m, s, E);
   }
   __syncthreads();
   const int64_t n = n0 + t;
   if (t < rows && n < N) {
     double* l = row + t * C;
-    double mx = l[0];
-    for (int k = 1; k < C; ++k) mx = fmax(mx, l[k]);
-    double s = 0.0;
-    for (int k = 0; k < C; ++k) { l[k] = exp(l[k] - mx); s += l[k]; }
-    double* __restrict__ p = probs + n * C;
-    for (int k = 0; k < C; ++k) { l[k] = l[k] / s; p[k] = l[k]; }
+    row_softmax(l, C, probs + n * C);
     row_max(l, C, n, labels, conf, pred, hit);
   }
 }

@@ -24,7 +24,7 @@ import torch
 from . import _capture
 
 __all__ = ("evaluate_model", "evaluate_ood", "predictive_tables", "logit_tables", "ensemble_across_chains",
-           "ensemble_metrics", "gather_samples", "evaluate_loo", "evaluate_marglik")
+           "ensemble_metrics", "gather_samples", "evaluate_loo", "evaluate_marglik", "evaluate_uncertainty")
 
 
 def _labels_of(dataloader):
@@ -468,6 +468,43 @@ def evaluate_ood(model, dataloader_train, dataloader_test, samples):
     auroc, auprc = calibration.auroc_auprc(calibration.ensemble_probs(acc_in).conf,
                                            calibration.ensemble_probs(acc_out).conf)
     return {"auroc": auroc, "auprc": auprc}
+
+
+def evaluate_uncertainty(model, dataloader_test, samples, dataloader_ood=None):
+    """How uncertain the posterior ensemble is on ``dataloader_test``, and what that uncertainty is worth
+    (uncertainty.py, on the device, fp64).  Plain floats.  Means over the rows: ``entropy`` (predictive),
+    ``expected_entropy`` (aleatoric), ``mutual_info`` (epistemic, BALD), ``disagreement``, ``nll``, ``brier``, ``acc``.
+    Selective prediction under the 0/1 loss: ``aurc`` / ``eaurc`` with the max-prob as the confidence,
+    ``aurc_mutual_info`` with the negated mutual information; ``error_auroc``: the AUROC of the max-prob telling the
+    correct rows (positive) from the wrong ones, NaN where there are none of either.  With ``dataloader_ood`` (its labels
+    are ignored): ``ood_auroc_<s>`` / ``ood_auprc_<s>`` for the scores s = ``max_prob``, ``entropy``, ``mutual_info``,
+    the test set being the positive class; ``ood_auroc_max_prob`` is ``evaluate_ood``'s ``auroc``.  The reference has no
+    such function."""
+    from . import calibration, uncertainty
+    loaders = (dataloader_test,) if dataloader_ood is None else (dataloader_test, dataloader_ood)
+    labels = _labels_of(dataloader_test)
+    if labels.dim() != 1 or labels.dtype.is_floating_point:
+        raise ValueError("uncertainty metrics need integer class labels")
+    tables = logit_tables(model, loaders, samples)
+    if tables[0].shape[1] != labels.shape[0]:
+        raise ValueError(f"{labels.shape[0]} labels but the loader yielded {tables[0].shape[1]} rows")
+    u = uncertainty.decompose(tables[0], labels.to(tables[0].device))
+    means = torch.stack([u.entropy, u.expected_entropy, u.mutual_info, u.disagreement, u.nll, u.brier,
+                         u.hit.to(torch.float64)]).mean(1).cpu().tolist()
+    out = dict(zip(("entropy", "expected_entropy", "mutual_info", "disagreement", "nll", "brier", "acc"), means))
+    wrong = 1 - u.hit
+    rc = uncertainty.risk_coverage(u.max_prob, wrong)
+    out["aurc"], out["eaurc"] = rc.aurc, rc.eaurc
+    out["aurc_mutual_info"] = uncertainty.risk_coverage(-u.mutual_info, wrong).aurc
+    right = u.hit.bool()
+    conf_right, conf_wrong = u.max_prob[right], u.max_prob[~right]
+    out["error_auroc"] = (calibration.auroc_auprc(conf_right, conf_wrong)[0]
+                          if conf_right.shape[0] and conf_wrong.shape[0] else math.nan)
+    if dataloader_ood is not None:
+        s_in, s_out = uncertainty.ood_scores(u), uncertainty.ood_scores(uncertainty.decompose(tables[1]))
+        for name in ("max_prob", "entropy", "mutual_info"):
+            out[f"ood_auroc_{name}"], out[f"ood_auprc_{name}"] = calibration.auroc_auprc(s_in[name], s_out[name])
+    return out
 
 
 @torch.no_grad()

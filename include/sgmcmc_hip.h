@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGMCMC_ABI_VERSION 16
+#define SGMCMC_ABI_VERSION 17
 #define SGMCMC_CHUNK 4096 /* default elements per arena chunk = 256 threads x 4 items x 4 elements */
 #define SGMCMC_CHUNK_SMALL 1024 /* small models: one item per thread, 4x more workgroups */
 #define SGMCMC_NSUMS 6
@@ -907,6 +907,56 @@ int sgmcmc_calibration_error(const double* keys, int64_t elem_stride, int64_t co
  * 2 area = sum dFP (TP_prev + TP) in integers, out[1] = sum (R_k - R_{k-1}) P_k over the thresholds in descending
  * order, out[2] = 1 if a score is NaN (out[0], out[1] NaN then), else 0.  0 < n_pos < n. */
 int sgmcmc_rank_metrics(const double* scores, const int32_t* perm, int n, int n_pos, double* out, void* stream);
+
+/* ---- Uncertainty of a posterior ensemble: entropy decomposition, proper scores, risk-coverage (fp64, deterministic) ---
+ * The reference has no such function; this is the definition.
+ *
+ * sgmcmc_uncertainty_rows: one pass over acc [samples][rows][classes] = [E][N][C], per-sample NORMALISED
+ * log-probabilities (the table of sgmcmc_ensemble_probs, same precondition: the kernel does not renormalise, so a table
+ * whose rows do not sum to 1 under exp gives the formulas below applied to it as it stands).  Per row n:
+ *  1. probs[n, :], max_prob[n], pred[n], hit[n]: pbar = softmax(logsumexp_e acc[e, n, :] - log E), its maximum, the first
+ *     index of the maximum and pred == labels -- the very instruction sequence of sgmcmc_ensemble_probs: the same bits.
+ *  2. margin[n] = max_prob - (the largest pbar_c over c != pred): 0 when the maximum occurs twice; for C = 1 the second
+ *     largest is 0.
+ *  3. entropy[n] = -sum_c pbar_c log pbar_c, a term with pbar_c = 0 being 0 (nats).
+ *  4. expected_entropy[n] = -(sum_c h_c) / E with h_c = sum_e p log p, p = exp(acc[e, n, c]), the term of acc = -inf
+ *     being 0: the mean over the samples of each sample's own entropy.  h_c is formed as exp(m_c) sum_e x exp(x - m_c),
+ *     x = acc[e, n, c], on the running maximum m_c of 1.'s log-sum-exp and from its exponentials (rescaled by the same
+ *     factor whenever the maximum moves), so an entry costs one exp.  The samples are added in order of e; the sums
+ *     over the classes of 3. and 4. run in order of c with Neumaier's compensation (sum and carried error, added at
+ *     the end), which keeps a 128-term sum within an ulp or two of its exact value.
+ *  5. mutual_info[n] = entropy - expected_entropy, and 0 where that difference is negative (Jensen: it is not in exact
+ *     arithmetic; the clamp removes rounding of the order C eps).
+ *  6. disagreement[n] = #{e : first argmax_c acc[e, n, :] != pred[n]} / E, the count an integer.
+ *  7. with labels, y = labels[n]: nll[n] = -log pbar_y (+inf where pbar_y = 0); brier[n] = sum_c (pbar_c - [c == y])^2,
+ *     c ascending.  A label outside 0 .. C-1 names a class of probability 0: nll = +inf, brier = sum_c pbar_c^2.
+ * NaN rule: a NaN anywhere in the E x C entries of a row makes every probability of that row NaN, hence every
+ * floating-point output of the row (disagreement included); pred = 0 then (sgmcmc_row_max's rule: the first NaN wins)
+ * and hit = (labels[n] == 0).  Other rows are not touched.
+ * labels, hit, nll, brier: all four NULL or all four given.  Limits: 1 <= classes <= SGMCMC_CALIB_MAX_CLASSES,
+ * 1 <= samples, rows < 2^31; anything else, or a NULL pointer, returns hipErrorInvalidValue and launches nothing.
+ * One launch; the table is read once (8 E N C bytes); every output entry is written. */
+int sgmcmc_uncertainty_rows(const double* acc, const int64_t* labels, int samples, int rows, int classes, double* probs,
+                            double* max_prob, int64_t* pred, int64_t* hit, double* margin, double* entropy,
+                            double* expected_entropy, double* mutual_info, double* disagreement, double* nll,
+                            double* brier, void* stream);
+/* Risk-coverage curve of selective prediction.  scores [n]: higher = more confident; losses [n]: any fp64 values (1 - hit,
+ * nll, ...); perm = sgmcmc_stable_order of scores (one column).  Rank k = 1 .. n counts the rows from the most confident
+ * down.  Rows of equal score (-0.0 == 0.0) form a tie group of ranks (a, b]; with P(i) the sum of the losses of the first
+ * i ranks,
+ *     cum(k) = P(a) + (k - a) (P(b) - P(a)) / (b - a)   for a < k <= b,     risk[k - 1] = cum(k) / k,
+ * the expectation of the selective risk at coverage k / n over a uniformly random order inside every tie group, so the
+ * curve does not depend on the order of the rows.  It is evaluated as one division,
+ * ((b - a) P(a) + (k - a) (P(b) - P(a))) / ((b - a) k): for integer-valued losses numerator and denominator are exact,
+ * risk[k - 1] is the correctly rounded rational, and a permutation of the rows changes no bit.  P(b) == P(a) counts as a
+ * group sum of 0 (also where both are +inf, so that an infinite loss gives +inf from its rank on).
+ * out[0] = aurc = (sum_k risk[k - 1]) / n, out[1] = P(n) / n, the mean loss, out[2] = 1 if a score or a loss is NaN (then
+ * out[0], out[1] and every risk entry are NaN), else 0.
+ * Sums: the ranks are cut into 1024 consecutive chunks of ceil(n / 1024); P(i) = (the inclusive Hillis-Steele scan of the
+ * chunk totals, at the chunk before i's) + (the losses of i's chunk before i, in rank order); aurc adds each chunk's
+ * entries in rank order and then the 1024 chunk sums in order.  n <= SGMCMC_CALIB_MAX_ROWS.  One launch, one workgroup. */
+int sgmcmc_risk_coverage(const double* scores, const double* losses, const int32_t* perm, int n, double* risk,
+                         double* out, void* stream);
 
 /* ---- Between-chain diagnostics of stored draws: split-R-hat and effective sample size (fp64, deterministic) ----------
  * The reference has no such function; this is the definition (Gelman et al., BDA3 section 11.4-11.5; Geyer 1992;
