@@ -24,7 +24,7 @@ INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 SOURCES = [os.path.join(_HERE, "csrc", "sgmcmc_hip.hip")]
 SOURCE = SOURCES[0]
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 CHUNK = 4096
 CHUNK_SMALL = 1024
 NSUMS = 6
@@ -181,6 +181,7 @@ DIAG_MAX_SEQ, DIAG_MAX_CHAINS, DIAG_LAG_BLOCK, DIAG_TILE = 512, 64, 32, 32
 RANK_OWN, RANK_MAX_PROBS = 16, 3
 PSIS_MIN_DRAWS, PSIS_MAX_DRAWS, PSIS_MAX_TAIL, PSIS_OWN, PSIS_POINTWISE, PSIS_TOTALS = 5, 32768, 544, 16, 6, 9
 WEIGHTS_SLICE, WEIGHTS_MAX_MODELS, WEIGHTS_STATE, WEIGHTS_NOISE_PURPOSE = 1024, 32, 72, 4
+GMIX_TILE, GMIX_MAX_SAMPLES, GMIX_MAX_QUANTILES, PIT_MAX_LEVELS = 128, 32768, 64, 1024
 
 EXPORTS = {
     "sgmcmc_abi_version": (ctypes.c_int, []),
@@ -346,6 +347,14 @@ EXPORTS = {
     "sgmcmc_rank_metrics": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p] * 2),
     "sgmcmc_uncertainty_rows": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 12),
     "sgmcmc_risk_coverage": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int] + [ctypes.c_void_p] * 3),
+    "sgmcmc_gmix_workspace_bytes": (ctypes.c_int64, [ctypes.c_int] * 3),
+    "sgmcmc_gmix_rows": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int64] * 3 + [ctypes.c_void_p] + [ctypes.c_int] * 3
+                         + [ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 9),
+    "sgmcmc_gmix_quantiles": (ctypes.c_int, [ctypes.c_void_p] * 2 + [ctypes.c_int64] * 3 + [ctypes.c_int] * 3
+                              + [ctypes.c_void_p] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 2),
+    "sgmcmc_pit_calibration": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_void_p,
+                                              ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                              ctypes.c_int] + [ctypes.c_void_p] * 2),
     "sgmcmc_chain_rhat": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
                                          ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
     "sgmcmc_chain_ess": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,

@@ -1715,6 +1715,8 @@ int sgmcmc_debug_normals(float* out, int64_t start, int64_t n, uint64_t seed, ui
 #include "calib_hip.inc"
 // ... and the ensemble's uncertainty: entropy decomposition, disagreement, proper scores, risk-coverage curves (fp64)
 #include "uncert_hip.inc"
+// ... and a regression posterior's predictive scores: CRPS, PIT, log density, variance split, quantiles (fp64)
+#include "regress_hip.inc"
 // between-chain diagnostics of stored draws: split-R-hat and effective sample size (fp64)
 #include "diag_hip.inc"
 // ... and their rank-normalised form: normal scores of the average ranks, tail quantiles and indicators (fp64)

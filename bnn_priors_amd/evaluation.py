@@ -24,7 +24,8 @@ import torch
 from . import _capture
 
 __all__ = ("evaluate_model", "evaluate_ood", "predictive_tables", "logit_tables", "ensemble_across_chains",
-           "ensemble_metrics", "gather_samples", "evaluate_loo", "evaluate_marglik", "evaluate_uncertainty")
+           "ensemble_metrics", "gather_samples", "evaluate_loo", "evaluate_marglik", "evaluate_uncertainty",
+           "regression_tables", "evaluate_regression")
 
 
 def _labels_of(dataloader):
@@ -504,6 +505,73 @@ def evaluate_uncertainty(model, dataloader_test, samples, dataloader_ood=None):
         s_in, s_out = uncertainty.ood_scores(u), uncertainty.ood_scores(uncertainty.decompose(tables[1]))
         for name in ("max_prob", "entropy", "mutual_info"):
             out[f"ood_auroc_{name}"], out[f"ood_auprc_{name}"] = calibration.auroc_auprc(s_in[name], s_out[name])
+    return out
+
+
+@torch.no_grad()
+def regression_tables(model, dataloader, samples):
+    """The Gaussian predictions of every sample on ``dataloader``: (mean [E, N, D], scale [E, N, D], y [N, D]), float64 on
+    the model's device -- ``preds.mean`` / ``preds.scale`` of ``model(x)`` with each sample loaded in turn, as
+    ``predictive_tables`` loads them; the model is left holding the last sample.  ``ValueError`` for a likelihood that
+    is not Normal."""
+    device = next(iter(model.parameters())).device
+    E = _n_samples(samples)
+    mean = scale = y = None
+    for e in range(E):
+        model.load_state_dict({k: v[e] for k, v in samples.items()})
+        means, scales, ys = [], [], []
+        for bx, by in dataloader:
+            preds = model(bx.to(device))
+            if not isinstance(preds, torch.distributions.Normal):
+                raise ValueError(f"regression scores need a Normal likelihood, not {type(preds)}")
+            m = preds.mean
+            means.append(m.reshape(len(bx), -1))
+            scales.append(preds.scale.expand_as(m).reshape(len(bx), -1))
+            if e == 0:
+                ys.append(by.to(device).reshape(len(bx), -1))
+        m, s = torch.cat(means), torch.cat(scales)
+        if e == 0:
+            y = torch.cat(ys).to(torch.float64)
+            if y.shape != m.shape:
+                raise ValueError(f"targets of shape {tuple(y.shape)} but predictions of shape {tuple(m.shape)}")
+            mean = torch.empty((E,) + tuple(m.shape), dtype=torch.float64, device=device)
+            scale = torch.empty_like(mean)
+        elif m.shape != mean.shape[1:]:
+            raise ValueError("the loader yielded a different number of rows for another sample")
+        mean[e], scale[e] = m, s
+    return mean, scale, y
+
+
+def evaluate_regression(model, dataloader_test, samples, central=(0.5, 0.9, 0.95)):
+    """How good the posterior predictive of a regression model is on ``dataloader_test`` (regression.py, on the device,
+    fp64): per row and output the equal-weight mixture of the samples' Gaussians.  Plain floats, means over rows and
+    outputs: ``rmse`` (the root of the mean squared error of the mixture's mean), ``lpd``, ``crps``, ``var_aleatoric``,
+    ``var_epistemic``; ``pit_ks`` and ``calibration_error`` (of the PIT values at ``regression.DEFAULT_LEVELS``) per
+    output and then averaged; per level c of ``central`` the interval between the mixture's quantiles at (1 -+ c) / 2:
+    ``coverage_<c>`` (the share of targets inside), ``width_<c>`` and ``interval_score_<c>`` (Winkler).  The reference
+    has no such function."""
+    from . import regression
+    central = [float(c) for c in central]
+    if not all(0.0 < c < 1.0 for c in central):
+        raise ValueError("every central level must lie strictly between 0 and 1")
+    mean, scale, y = regression_tables(model, dataloader_test, samples)
+    g = regression.predictive(mean, scale, y)
+    n = len(central)
+    stats = [g.sq_err.mean(), g.lpd.mean(), g.crps.mean(), g.var_aleatoric.mean(), g.var_epistemic.mean()]
+    if n:
+        q = regression.quantiles(mean, scale, [(1.0 - c) / 2.0 for c in central] + [(1.0 + c) / 2.0 for c in central])
+        for i, c in enumerate(central):
+            lo, hi = q[i], q[n + i]
+            stats += [((lo <= y) & (y <= hi)).sum().to(torch.float64), (hi - lo).mean(),      # (an integer count)
+                      regression.interval_score(lo, hi, y, c).mean()]
+    regression._check_pit(g.pit, 2)
+    table = regression._pit_columns(g.pit, list(regression.DEFAULT_LEVELS), [])
+    vals = torch.stack(stats).cpu().tolist()
+    out = {"rmse": math.sqrt(vals[0]), "lpd": vals[1], "crps": vals[2], "pit_ks": table[:, 0].mean().item(),
+           "calibration_error": table[:, 1].mean().item(), "var_aleatoric": vals[3], "var_epistemic": vals[4]}
+    for i, c in enumerate(central):
+        inside, width, score = vals[5 + 3 * i:8 + 3 * i]
+        out[f"coverage_{c:g}"], out[f"width_{c:g}"], out[f"interval_score_{c:g}"] = inside / y.numel(), width, score
     return out
 
 

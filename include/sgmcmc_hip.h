@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGMCMC_ABI_VERSION 17
+#define SGMCMC_ABI_VERSION 18
 #define SGMCMC_CHUNK 4096 /* default elements per arena chunk = 256 threads x 4 items x 4 elements */
 #define SGMCMC_CHUNK_SMALL 1024 /* small models: one item per thread, 4x more workgroups */
 #define SGMCMC_NSUMS 6
@@ -957,6 +957,76 @@ int sgmcmc_uncertainty_rows(const double* acc, const int64_t* labels, int sample
  * entries in rank order and then the 1024 chunk sums in order.  n <= SGMCMC_CALIB_MAX_ROWS.  One launch, one workgroup. */
 int sgmcmc_risk_coverage(const double* scores, const double* losses, const int32_t* perm, int n, double* risk,
                          double* out, void* stream);
+
+/* ---- Predictive scores of a regression posterior: CRPS, PIT, log density, variance split, quantiles (fp64, --------
+ * deterministic).  The reference has no such function; this is the definition.
+ *
+ * mean [samples][rows][outputs] = [E][N][D], contiguous: the samples' predictive means.  scale: their standard
+ * deviations, element (e, n, d) at scale[e * scale_se + n * scale_sn + d * scale_sd]; any stride may be 0, so that a
+ * noise level per sample ([E]), per sample and output ([E, D]) or per entry ([E, N, D]) is read where it lies.  Per entry
+ * (n, d) the posterior predictive is the equal-weight mixture of Normal(mu_e, sigma_e), with the CDF
+ *     F(x) = (1/E) sum_e Phi((x - mu_e) / sigma_e),   Phi(z) = erfc(-z / sqrt 2) / 2   (both tails keep their accuracy).
+ *
+ * sgmcmc_gmix_rows, per entry:
+ *  1. pred_mean = mbar = (sum_e mu_e) / E.
+ *  2. var_aleatoric = (sum_e sigma_e^2) / E; var_epistemic = (sum_e (mu_e - mbar)^2) / E, in a second pass over the
+ *     samples; var_total = var_aleatoric + var_epistemic, the mixture's variance.
+ *  with y [N][D] (y, sq_err, lpd, pit, crps: all five NULL or all five given):
+ *  3. sq_err = (y - mbar)^2.
+ *  4. lpd = log (1/E) sum_e N(y; mu_e, sigma_e), the log-sum-exp of -z_e^2 / 2 - log sigma_e - log(2 pi) / 2 with
+ *     z_e = (y - mu_e) / sigma_e, minus log E.
+ *  5. pit = F(y).
+ *  6. crps = (1/E) sum_i A(y - mu_i, sigma_i) - (1/E^2) [ sum_{i<j} A(mu_i - mu_j, sqrt(sigma_i^2 + sigma_j^2))
+ *            + sum_i sigma_i / sqrt(pi) ],   A(m, s) = m erf(m / (s sqrt 2)) + 2 s phi(m / s) = E|Normal(m, s)|:
+ *     the closed form of  integral (F(x) - 1[x >= y])^2 dx  for a Gaussian mixture (Grimit et al. 2006).
+ * Sums.  The samples are dealt to 16 slices (e mod 16); a slice adds its terms in order of e with Neumaier's
+ * compensation and the 16 slice sums are added in slice order, compensated again; the log-sum-exp runs per slice
+ * and the slices are merged on their common maximum in slice order.  The pair sum of 6. cuts the samples into tiles of
+ * SGMCMC_GMIX_TILE and an entry's triangle of tile pairs (I <= J, row by row) into S consecutive chunks, one workgroup
+ * each, S = min(ceil(2048 / (N D)), ceil(P / 2)) with P the number of tile pairs: a function of (E, N, D) alone.  A thread
+ * owns one i of tile I and every second j of tile J, adds its terms in order with compensation, the workgroup's 256
+ * sums are added in an error-free (two-sum) tree, and the S partials of an entry are added in order as above.  Two
+ * calls give the same bits.
+ * NaN rule: a NaN among an entry's mu_e or its y, or a sigma_e that is not > 0, makes every floating-point output of that
+ * entry NaN; other entries are not touched.
+ * workspace: sgmcmc_gmix_workspace_bytes(samples, rows, outputs) bytes (-1 for sizes outside the limits), needed with
+ * y only.  Limits: 1 <= samples <= SGMCMC_GMIX_MAX_SAMPLES, 1 <= rows, outputs, rows * outputs <= 2^30; anything
+ * else, a negative stride or a missing pointer returns hipErrorInvalidValue and launches nothing.  Two launches with
+ * y (E^2 / 2 erf + exp per entry), one without; nothing synchronises with the host. */
+#define SGMCMC_GMIX_TILE 128
+#define SGMCMC_GMIX_MAX_SAMPLES 32768
+#define SGMCMC_GMIX_MAX_QUANTILES 64
+#define SGMCMC_PIT_MAX_LEVELS 1024
+int64_t sgmcmc_gmix_workspace_bytes(int samples, int rows, int outputs);
+int sgmcmc_gmix_rows(const double* mean, const double* scale, int64_t scale_se, int64_t scale_sn, int64_t scale_sd,
+                     const double* y, int samples, int rows, int outputs, void* workspace, int64_t workspace_bytes,
+                     double* pred_mean, double* var_aleatoric, double* var_epistemic, double* var_total, double* sq_err,
+                     double* lpd, double* pit, double* crps, void* stream);
+/* Quantiles of the same mixtures: out[j][n][d] = q with F(q) = probs[j], j < n_probs <= SGMCMC_GMIX_MAX_QUANTILES, probs
+ * and z = Phi^-1(probs) in DEVICE memory (fp64; the caller supplies z).  The root lies in the hull of the components' own
+ * quantiles, lo = min_e (mu_e + sigma_e z) and hi = max_e (mu_e + sigma_e z): F(lo) <= p <= F(hi).  An end whose F already
+ * meets p (lo == hi, as for E = 1; F(lo) >= p; F(hi) <= p) is returned as it stands -- E = 1 gives mu + sigma z.  Else the
+ * bracket is refined by the secant through its ends (Illinois: the weight of an end kept twice is halved), by its
+ * midpoint whenever the step before did not halve it or the secant point is not inside, until the ends are adjacent
+ * doubles or F(x) == p, and for at most 256 steps; the end with the smaller |F - p| is returned (the lower on a tie).
+ * Every F is the slice-wise sum of sgmcmc_gmix_rows' 5.  The NaN rule and the limits are sgmcmc_gmix_rows'. */
+int sgmcmc_gmix_quantiles(const double* mean, const double* scale, int64_t scale_se, int64_t scale_sn, int64_t scale_sd,
+                          int samples, int rows, int outputs, const double* probs, const double* z, int n_probs,
+                          double* out, void* stream);
+/* Calibration of PIT values u (one column per output; column c's value i at pit[c * col_stride + i * elem_stride], perm =
+ * sgmcmc_stable_order of the columns), one workgroup per column.  With u_(1) <= ... <= u_(n) and W = 3 + n_levels +
+ * n_central, out[c * W + ...]:
+ *  [0] the Kolmogorov-Smirnov distance to the uniform, max_k max(k / n - u_(k), u_(k) - (k - 1) / n);
+ *  [1] the calibration error of Kuleshov et al. 2018, (1 / n_levels) sum_j (count_j / n - levels[j])^2, the terms added
+ *      in a fixed binary tree;
+ *  [2] 1 if the column holds a NaN (then every other entry of the column's out is NaN), else 0;
+ *  [3 + j] count_j = #{u <= levels[j]}, an integer;
+ *  [3 + n_levels + i] #{(1 - c_i) / 2 <= u <= (1 + c_i) / 2} for c_i = central[i], an integer.
+ * levels, central: DEVICE memory.  1 <= n <= SGMCMC_CALIB_MAX_ROWS, 1 <= n_levels <= SGMCMC_PIT_MAX_LEVELS,
+ * 0 <= n_central <= SGMCMC_PIT_MAX_LEVELS, ncols <= 65535.  One launch. */
+int sgmcmc_pit_calibration(const double* pit, int64_t elem_stride, int64_t col_stride, const int32_t* perm, int n,
+                           int ncols, const double* levels, int n_levels, const double* central, int n_central,
+                           double* out, void* stream);
 
 /* ---- Between-chain diagnostics of stored draws: split-R-hat and effective sample size (fp64, deterministic) ----------
  * The reference has no such function; this is the definition (Gelman et al., BDA3 section 11.4-11.5; Geyer 1992;
