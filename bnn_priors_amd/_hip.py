@@ -24,7 +24,7 @@ INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 SOURCES = [os.path.join(_HERE, "csrc", "sgmcmc_hip.hip")]
 SOURCE = SOURCES[0]
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 CHUNK = 4096
 CHUNK_SMALL = 1024
 NSUMS = 6
@@ -182,6 +182,15 @@ RANK_OWN, RANK_MAX_PROBS = 16, 3
 PSIS_MIN_DRAWS, PSIS_MAX_DRAWS, PSIS_MAX_TAIL, PSIS_OWN, PSIS_POINTWISE, PSIS_TOTALS = 5, 32768, 544, 16, 6, 9
 WEIGHTS_SLICE, WEIGHTS_MAX_MODELS, WEIGHTS_STATE, WEIGHTS_NOISE_PURPOSE = 1024, 32, 72, 4
 GMIX_TILE, GMIX_MAX_SAMPLES, GMIX_MAX_QUANTILES, PIT_MAX_LEVELS = 128, 32768, 64, 1024
+FIT_TILE_DOUBLES, FIT_TILE_ROWS, FIT_MAX_BLOCKS, FIT_PART, FIT_STATE = 5120, 512, 1024, 408, 1288
+
+
+class FitGeometry(ctypes.Structure):
+    "sgmcmc_fit_geometry"
+    _fields_ = [("P", ctypes.c_int32), ("F", ctypes.c_int32), ("f_major", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("events", ctypes.c_int64), ("size", ctypes.c_int64 * 4), ("stride", ctypes.c_int64 * 4),
+                ("f_stride", ctypes.c_int64), ("pos", ctypes.c_int64 * FILTER_MAX_P)]
+
 
 EXPORTS = {
     "sgmcmc_abi_version": (ctypes.c_int, []),
@@ -389,6 +398,15 @@ EXPORTS = {
     "sgmcmc_bb_pseudo_bma": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
                                             ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p,
                                             ctypes.c_int64] + [ctypes.c_void_p] * 4),
+    "sgmcmc_fit_blocks": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int64]),
+    "sgmcmc_fit_moments": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(FitGeometry), ctypes.c_int]
+                           + [ctypes.c_void_p] * 5),
+    "sgmcmc_fit_mvt_init": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double,
+                                           ctypes.c_void_p, ctypes.c_void_p]),
+    "sgmcmc_fit_mvt_iterate": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(FitGeometry), ctypes.c_int,
+                                              ctypes.c_int64] + [ctypes.c_double] * 3 + [ctypes.c_void_p] * 5),
+    "sgmcmc_fit_abs_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(FitGeometry), ctypes.c_double,
+                                            ctypes.c_double] + [ctypes.c_void_p] * 5),
     "sgmcmc_debug_normals": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                             ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64,
                                             ctypes.c_uint32, ctypes.c_void_p]),

@@ -1725,3 +1725,5 @@ int sgmcmc_debug_normals(float* out, int64_t start, int64_t n, uint64_t seed, ui
 #include "psis_hip.inc"
 // model-averaging weights from the pointwise elpd rows: stacking, pseudo-BMA, pseudo-BMA+ and mixture densities (fp64)
 #include "weights_hip.inc"
+// the data-driven priors fitted to stacks of weight samples: moments, multivariate-t EM, element-wise families (fp64)
+#include "fit_hip.inc"

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGMCMC_ABI_VERSION 18
+#define SGMCMC_ABI_VERSION 19
 #define SGMCMC_CHUNK 4096 /* default elements per arena chunk = 256 threads x 4 items x 4 elements */
 #define SGMCMC_CHUNK_SMALL 1024 /* small models: one item per thread, 4x more workgroups */
 #define SGMCMC_NSUMS 6
@@ -1248,6 +1248,81 @@ int sgmcmc_pseudo_bma(const double* P, int64_t model_stride, int models, int64_t
 int sgmcmc_bb_pseudo_bma(const double* P, int64_t model_stride, int models, int64_t observations, int64_t replicates,
                          uint64_t seed, uint32_t noise_stream, void* workspace, int64_t workspace_bytes, double* z,
                          double* w, double* out, void* stream);
+
+/* ---- Fitting the data-driven priors to stacks of weight samples (fp64, deterministic) ----------------------------------
+ * The reference fits its priors offline (scipy); this is the definition, restated in tests/prior_fit_reference.py.
+ * A stack w [S, *shape] (fp32 or fp64) is read in place through a GEOMETRY: `events` events, numbered row-major over up
+ * to four event dimensions (size, stride in elements; unused ones are size 1), each of F vectors (vector f at
+ * f * f_stride) of P positions (position a at pos[a]).  Vector v = event * F + f; n = events * F vectors.  f_major != 0
+ * tells the loader that f_stride exceeds the innermost event stride, so that a tile is walked f-first (coalesced along
+ * the stack's fastest dimension); it changes no result.  All arithmetic is fp64, every operation rounded once.
+ * Summation order: the events are cut into tiles of TE = max(1, min(SGMCMC_FIT_TILE_DOUBLES / (F (P | 1)),
+ * SGMCMC_FIT_TILE_ROWS / F)) events; workgroup b of sgmcmc_fit_blocks() takes tiles b, b + blocks, ...  An accumulated
+ * entry (of NE per pass) is cut into G = max(1, 256 / NE) slices; slice q adds rows (or events) q, q + G, ... of a tile
+ * from 0 in ascending order, the tiles' sums are added in ascending order (compensated, Neumaier), the slices from 0 in
+ * ascending order; of the workgroups' partials, slice q adds workgroups q, q + G, ... (compensated), and the slices are
+ * added from 0 in ascending order.  Counts are integers.  No atomics.
+ *  1. Moments.  Shift c_a = the median of position a of vectors 0, n / 2, n - 1 (0 if not finite); d = x - c.  From
+ *     sum d_a, sum d_a d_b, sum d_a^3, sum d_a^4:  m = sum d / n;  mean = c + m;  cov_ab = (sum d_a d_b - sum d_a
+ *     (sum d_b / n)) / (n - ddof);  with s_k = sum d^k / n:  m2 = s2 - m^2;  m3 = s3 - 3 m s2 + 2 m^3;
+ *     m4 = s4 - 4 m s3 + 6 m^2 s2 - 3 m^4;  skew = m3 / m2^1.5;  kurt = m4 / m2^2 - 3 (population definitions; NaN for a
+ *     column with m2 <= 0, whose var is reported as 0).  Pooled over the n P elements with delta_a = mean_a - mean of
+ *     the means:  M2 = mean_a (m2 + delta^2), M3 = mean_a (m3 + 3 delta m2 + delta^3), M4 = mean_a (m4 + 4 delta m3
+ *     + 6 delta^2 m2 + delta^4).  out: mean [P], cov [P][P], skew [P], kurt [P], var [P] (= m2), pooled {mean, var, skew,
+ *     kurt}.  A non-finite element anywhere makes every output NaN; bad[0] counts them.
+ *  2. Multivariate t by EM, in the standard parametrisation (mu, S, nu): an event's F vectors share one mixing variable,
+ *     its scatter is I_F (x) S, D = F P.  State record, SGMCMC_FIT_STATE doubles: phase (0 iterating, 1 the pass at the
+ *     returned parameters is due, 2 finished), iterations, converged, nu, sum_a log L_aa, loglik, df_at_bound, the last
+ *     relative change, mu [25], L^-1 [25 x 25] and S [25 x 25] (row-major with row stride P; S = L L^T).  One iteration:
+ *       A (one pass):  M_i = sum_f |L^-1 (x_if - mu)|^2;  u_i = (nu + D) / (nu + M_i);  sum u_i;  A = sum u_i sum_f d_if;
+ *                      B = sum u_i sum_f d_if d_if^T;  sum (log u_i - u_i);  sum log1p(M_i / nu)
+ *       B (one workgroup):  trace[iterations] = loglik(mu, S, nu) = events (lgamma((nu + D) / 2) - lgamma(nu / 2)
+ *                      - D / 2 log(pi nu) - F sum log L_aa) - (nu + D) / 2 sum log1p(M_i / nu);  W = F sum u_i;
+ *                      mu' = mu + A / W;  S' = (B - A (A / W)^T) / W (parameter-expanded: Kent, Tyler & Vardi 1994);
+ *                      nu' = the root in [df_lo, df_hi] of log(nu'/2) - psi(nu'/2) + 1 + mean (log u_i - u_i)
+ *                      + psi((nu + D) / 2) - log((nu + D) / 2) (Liu & Rubin 1995), by Newton steps kept inside a
+ *                      bisection bracket until they move by less than 1e-15 nu' (the nearer bound if there is no root);
+ *                      delta = max(|nu' - nu| / nu', |mu' - mu|_a / sqrt(S'_aa), |S' - S|_ab / sqrt(S'_aa S'_bb)).
+ *     delta <= tol sets converged; then, or after max_iter iterations, one more pair A, B writes loglik at the returned
+ *     parameters and finishes.  A finished state turns A and B into no-ops, so the result does not depend on how the
+ *     iterations are batched.  A non-finite element, a non-finite log-likelihood or an S that is not positive definite
+ *     finishes the fit with NaN parameters (not converged).  lgamma, psi and psi' are the recurrence up to x >= 10 and
+ *     the asymptotic (Stirling) series through B_14.
+ *  3. Element-wise sums at a given loc and beta over a P = F = 1 geometry, d = |x - loc|: out = {sum d, sum log d,
+ *     sum d^beta, sum d^beta log d, sum d^beta log^2 d} over the elements with d > 0, d^beta = exp(beta log d);
+ *     zeros[0] = #{d == 0}.  Thread t of workgroup b adds elements b 256 + t, + blocks 256, ... (compensated), the
+ *     workgroup the fixed tree (t += t + 128, ..., t + 1).
+ * The caller provides every buffer (part: (blocks + 1) * SGMCMC_FIT_PART doubles, counts: blocks int64); nothing is
+ * allocated, nothing synchronises.  Limits: 1 <= P <= SGMCMC_FILTER_MAX_P, 1 <= F <= SGMCMC_FIT_TILE_ROWS,
+ * F (P | 1) <= SGMCMC_FIT_TILE_DOUBLES, events F < 2^31, strides and offsets >= 0, the product of the sizes = events;
+ * anything else or a NULL pointer returns hipErrorInvalidValue and launches nothing. */
+#define SGMCMC_FIT_TILE_DOUBLES 5120
+#define SGMCMC_FIT_TILE_ROWS 512
+#define SGMCMC_FIT_MAX_BLOCKS 1024
+#define SGMCMC_FIT_PART 408
+#define SGMCMC_FIT_STATE 1288
+typedef struct sgmcmc_fit_geometry {
+  int32_t P, F, f_major, reserved;
+  int64_t events;
+  int64_t size[4], stride[4];
+  int64_t f_stride;
+  int64_t pos[SGMCMC_FILTER_MAX_P];
+} sgmcmc_fit_geometry;
+
+/* Workgroups of a pass (= partial records), a function of the sizes alone; -1 for a refused shape. */
+int sgmcmc_fit_blocks(int P, int F, int64_t events);
+/* Definition 1: one pass and one workgroup that adds its partials.  out [P P + 4 P + 4], bad [1]. */
+int sgmcmc_fit_moments(const void* w, int dtype, const sgmcmc_fit_geometry* geometry, int ddof, double* part,
+                       int64_t* counts, double* out, int64_t* bad, void* stream);
+/* Writes the state record of definition 2: mu = mean [P], S = cov [P][P] (df - 2) / df, nu = df > 2.  One launch. */
+int sgmcmc_fit_mvt_init(int P, const double* mean, const double* cov, double df, double* state, void* stream);
+/* Enqueues `iters` pairs A, B of definition 2; trace holds max_iter doubles.  max_iter + 1 pairs always finish. */
+int sgmcmc_fit_mvt_iterate(const void* w, int dtype, const sgmcmc_fit_geometry* geometry, int iters, int64_t max_iter,
+                           double tol, double df_lo, double df_hi, double* part, int64_t* counts, double* state,
+                           double* trace, void* stream);
+/* Definition 3: out [5], zeros [1].  Two launches. */
+int sgmcmc_fit_abs_stats(const void* w, int dtype, const sgmcmc_fit_geometry* geometry, double loc, double beta,
+                         double* part, int64_t* counts, double* out, int64_t* zeros, void* stream);
 
 /* Test hook: out[i] = spec normal (fp32) of noise index start+i. */
 int sgmcmc_debug_normals(float* out, int64_t start, int64_t n, uint64_t seed, uint32_t stream,
