@@ -24,7 +24,7 @@ INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 SOURCES = [os.path.join(_HERE, "csrc", "sgmcmc_hip.hip")]
 SOURCE = SOURCES[0]
 
-ABI_VERSION = 19
+ABI_VERSION = 20
 CHUNK = 4096
 CHUNK_SMALL = 1024
 NSUMS = 6
@@ -179,6 +179,7 @@ class DenseChain(ctypes.Structure):
 MAX_CHAINS, MLP_BATCH_MULTI = 8, 128
 DIAG_MAX_SEQ, DIAG_MAX_CHAINS, DIAG_LAG_BLOCK, DIAG_TILE = 512, 64, 32, 32
 RANK_OWN, RANK_MAX_PROBS = 16, 3
+SUMMARY_MAX_DRAWS, SUMMARY_MAX_TILE = 16384, 64
 PSIS_MIN_DRAWS, PSIS_MAX_DRAWS, PSIS_MAX_TAIL, PSIS_OWN, PSIS_POINTWISE, PSIS_TOTALS = 5, 32768, 544, 16, 6, 9
 WEIGHTS_SLICE, WEIGHTS_MAX_MODELS, WEIGHTS_STATE, WEIGHTS_NOISE_PURPOSE = 1024, 32, 72, 4
 GMIX_TILE, GMIX_MAX_SAMPLES, GMIX_MAX_QUANTILES, PIT_MAX_LEVELS = 128, 32768, 64, 1024
@@ -378,6 +379,20 @@ EXPORTS = {
     "sgmcmc_chain_tail_indicators": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
                                                     ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int]
                                      + [ctypes.c_void_p] * 5),
+    "sgmcmc_summary_tile_quantities": (ctypes.c_int, [ctypes.c_int]),
+    "sgmcmc_summary_sort": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
+                                           ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    "sgmcmc_summary_moments": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
+                                              ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int]
+                               + [ctypes.c_void_p] * 6),
+    "sgmcmc_summary_quantile": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                               ctypes.c_double, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    "sgmcmc_summary_hdi": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                          ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "sgmcmc_summary_mcse": (ctypes.c_int, [ctypes.c_void_p] * 5 + [ctypes.c_int64] + [ctypes.c_void_p] * 3),
+    "sgmcmc_summary_mcse_quantile": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                    ctypes.c_double, ctypes.c_void_p, ctypes.c_int64]
+                                     + [ctypes.c_void_p] * 6),
     "sgmcmc_psis_workspace_bytes": (ctypes.c_int64, [ctypes.c_int, ctypes.c_int64, ctypes.c_int]),
     "sgmcmc_psis_loo": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
                                        ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]

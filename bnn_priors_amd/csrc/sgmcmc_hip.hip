@@ -1721,6 +1721,8 @@ int sgmcmc_debug_normals(float* out, int64_t start, int64_t n, uint64_t seed, ui
 #include "diag_hip.inc"
 // ... and their rank-normalised form: normal scores of the average ranks, tail quantiles and indicators (fp64)
 #include "rank_hip.inc"
+// ... and what the posterior is: an LDS sorting network, moments, quantiles, the HDI and their Monte Carlo errors (fp64)
+#include "summary_hip.inc"
 // model comparison from the same tables: PSIS-LOO with Pareto-k and WAIC, pointwise and in total (fp64)
 #include "psis_hip.inc"
 // model-averaging weights from the pointwise elpd rows: stacking, pseudo-BMA, pseudo-BMA+ and mixture densities (fp64)

@@ -1,0 +1,509 @@
+// Posterior summaries of stored draws with their Monte Carlo standard errors: mean, sd, quantiles, the highest-density
+// interval, and the MCSE of the mean, the sd and every quantile (Vehtari, Gelman, Simpson, Carpenter, Buerkner 2021; the R
+// package posterior; ArviZ's unimodal HDI).  include/sgmcmc_hip.h states the definition.  The effective sample sizes
+// are diag::ess_kernel as it is, applied to the draws, to c^2 and to the indicators 1[v <= q_p]
+// (rankdiag::indicator_kernel as it is); this file has the steps that those do not have.
+//
+// x[m][s][q] and the J sequences of n draws are diag::Seqs; N = J n, draw i = j n + s in sequence order.
+//
+//   sort_kernel      the project's sorting kernel: a workgroup stages an [N_pad][TQ] fp64 tile of TQ columns in LDS
+//                    (N_pad = the next power of two, TQ = tile_quantities(N): 128 KiB at most), sorts every column
+//                    along N with a bitonic network, N_pad log2(N_pad) (log2(N_pad) + 1) / 4 compare-exchanges per column,
+//                    and writes sorted[i][q].  Whether a column has a non-finite draw is decided on load, before the
+//                    padding rows are filled with +inf: such a column is written as NaN, so a real +inf is never taken
+//                    for padding.  Zeros are staged as +0.0.
+//                    LDS layout: q is the fastest index of the tile AND of the thread numbering.  A compare-exchange
+//                    step with distance j pairs row i (bit j clear) with row i + j; thread p takes column p % TQ of
+//                    pair p / TQ, and consecutive pairs are consecutive rows within runs of j.  The 32 lanes that
+//                    ds_read_b64 serves together therefore read runs of j TQ consecutive doubles: one whole 256-byte
+//                    bank row without a conflict whenever j TQ >= 32, and runs separated by gaps of their own length,
+//                    a 2-way conflict at worst, in the last few steps of every merge.  The walk along N with lane = row,
+//                    at a stride of TQ doubles (32 lanes on 32 / TQ bank pairs: TQ-way, 32-way from TQ = 32 on), does
+//                    not occur: no lane group ever strides along N.  Global loads and stores run along q as well.
+//   moments_kernel   lane = quantity, thread group = one of the partial sums: the mean, then c = v - mean, m2, m4 and
+//                    the c^2 array, two reads of the column
+//   quantile_kernel  the type-7 quantile of one probability from two rows of the sorted array, in rankdiag's arithmetic
+//   hdi_kernel       lane = quantity: the narrowest window of k + 1 consecutive order statistics, first minimum
+//   mcse_kernel      mcse_mean and mcse_sd from the moments and the two ESS; the constant-column rule
+//   mcse_quantile_kernel   lane = quantity: alpha, beta from ess_q, the inverse regularised incomplete beta function at
+//                    Phi(-1) and Phi(1), the two ranks, and half the distance of their order statistics
+//
+// No atomics; every sum in an order fixed by N; a quantity's result is a function of its own column only, whatever the
+// grid, the tile or the chunk.
+
+namespace summary {
+
+constexpr int kMaxDraws = SGMCMC_SUMMARY_MAX_DRAWS;           // N
+constexpr int kMaxTile = SGMCMC_SUMMARY_MAX_TILE;             // TQ at most
+constexpr int kWays = SGMCMC_DIAG_MEAN_WAYS;                  // partial sums of every sum over the draws
+constexpr int kSortThreads = 1024;
+constexpr int kThreads = 256;
+constexpr int kMomentTile = kThreads / kWays;                 // quantities per workgroup of the moments pass
+constexpr double kLowerTail = 0.1586553, kUpperTail = 0.8413447;      // Phi(-1), Phi(1) as posterior writes them
+static_assert((kMaxDraws & (kMaxDraws - 1)) == 0 && (kMaxTile & (kMaxTile - 1)) == 0, "powers of two");
+static_assert((size_t)kMaxDraws * sizeof(double) == 128 * 1024, "one column of the most draws is the whole tile");
+static_assert((size_t)kMaxDraws * sizeof(double) + kMaxTile * sizeof(int) <= 160 * 1024, "LDS ceiling");
+
+inline int padded(int N) {
+  int p = 4;
+  while (p < N) p <<= 1;
+  return p;
+}
+
+// quantities per workgroup of the sort: the most columns of N_pad fp64 that fit 128 KiB, kMaxTile at most
+inline int tile_quantities(int N) {
+  if (N < 4 || N > kMaxDraws) return 0;
+  const int t = kMaxDraws / padded(N);
+  return t < kMaxTile ? t : kMaxTile;
+}
+
+inline bool make_seqs(int64_t chain_stride, int64_t draw_stride, int chains, int draws, int64_t quantities, int split,
+                      diag::Seqs* A) {
+  return diag::make_seqs(chain_stride, draw_stride, chains, draws, quantities, split, A) && A->J * A->n <= kMaxDraws;
+}
+
+__device__ __forceinline__ double plus_zero(double v) { return v == 0.0 ? 0.0 : v; }      // -0.0 is written as +0.0
+__device__ __forceinline__ bool is_finite(double v) { return fabs(v) < INFINITY; }         // false for NaN as well
+
+template <typename T>
+__global__ __launch_bounds__(kSortThreads) void sort_kernel(const T* __restrict__ x, diag::Seqs A, int64_t Q, int N,
+                                                            int n_pad, int log_tq, double* __restrict__ sorted) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char summary_lds[];
+  double* __restrict__ tile = reinterpret_cast<double*>(summary_lds);             // [n_pad][tq]
+  const int tq = 1 << log_tq, cells = n_pad << log_tq;
+  int* __restrict__ bad = reinterpret_cast<int*>(tile + cells);                   // [tq]: the column has a non-finite draw
+  const int t = threadIdx.x;
+  const int64_t q0 = (int64_t)blockIdx.x << log_tq;
+
+  if (t < tq) bad[t] = 0;
+  __syncthreads();
+  for (int e = t; e < cells; e += kSortThreads) {
+    const int i = e >> log_tq, c = e & (tq - 1);
+    double v = INFINITY;                          // padding: after every finite value
+    if (i < N) {
+      v = 0.0;                                    // a column past the end of the call: sorted, never stored
+      if (q0 + c < Q) {
+        const int j = i / A.n, s = i - j * A.n;
+        v = plus_zero((double)x[diag::seq_offset(A, j) + (int64_t)s * A.draw_stride + q0 + c]);
+        if (!is_finite(v)) bad[c] = 1;            // every writer stores the same value
+      }
+    }
+    tile[e] = v;
+  }
+
+  const int pairs = cells >> 1;
+  for (int k = 2; k <= n_pad; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      __syncthreads();
+      for (int p = t; p < pairs; p += kSortThreads) {
+        const int c = p & (tq - 1), pr = p >> log_tq;
+        const int i = ((pr & ~(j - 1)) << 1) | (pr & (j - 1));        // bit j clear; the partner is i + j
+        const int lo = (i << log_tq) | c, hi = ((i | j) << log_tq) | c;
+        const double a = tile[lo], b = tile[hi];
+        const bool ascending = (i & k) == 0;                           // always in the last merge, k = n_pad
+        if (ascending ? a > b : a < b) {
+          tile[lo] = b;
+          tile[hi] = a;
+        }
+      }
+    }
+  }
+  __syncthreads();
+
+  for (int e = t; e < (N << log_tq); e += kSortThreads) {
+    const int i = e >> log_tq, c = e & (tq - 1);
+    if (q0 + c < Q) sorted[(int64_t)i * Q + q0 + c] = bad[c] ? NAN : tile[e];
+  }
+}
+
+// draw i of the column at xq, in sequence order, widened
+template <typename T>
+__device__ __forceinline__ double draw(const T* __restrict__ xq, const diag::Seqs& A, int i) {
+  const int j = i / A.n, s = i - j * A.n;
+  return plus_zero((double)xq[diag::seq_offset(A, j) + (int64_t)s * A.draw_stride]);
+}
+
+// Every sum over the draws i = 0 .. N-1: kWays partial sums over i = r (mod kWays), each in ascending i from +0.0, the
+// partials added in ascending r, every addition rounded once.  Thread group r of the workgroup forms partial r of the
+// kMomentTile quantities (lane = quantity); the partials meet in LDS.
+template <typename T>
+__global__ __launch_bounds__(kThreads) void moments_kernel(const T* __restrict__ x, diag::Seqs A, int64_t Q,
+                                                           double* __restrict__ mean_out, double* __restrict__ sd_out,
+                                                           double* __restrict__ m2_out, double* __restrict__ m4_out,
+                                                           double* __restrict__ csq) {
+  __shared__ double part[3][kWays][kMomentTile];            // of sum v, sum c^2, sum c^4
+  __shared__ int flags[kWays][kMomentTile];                 // bit 0: every draw is finite, bit 1: every draw equals the first
+  const int lane = threadIdx.x % kMomentTile, way = threadIdx.x / kMomentTile;
+  const int64_t q = (int64_t)blockIdx.x * kMomentTile + lane;
+  const bool live = q < Q;
+  const int N = A.J * A.n;
+  const double Nd = (double)N;
+  const T* __restrict__ xq = x + (live ? q : 0);
+  const double first = live ? draw(xq, A, 0) : 0.0;
+
+  double p = 0.0;
+  bool finite = true, constant = true;
+  if (live) {
+    for (int i = way; i < N; i += kWays) {
+      const double v = draw(xq, A, i);
+      finite = finite && is_finite(v);
+      constant = constant && v == first;
+      p = __dadd_rn(p, v);
+    }
+  }
+  part[0][way][lane] = p;
+  flags[way][lane] = (finite ? 1 : 0) | (constant ? 2 : 0);
+  __syncthreads();
+  double sum = part[0][0][lane];
+  int all = flags[0][lane];
+#pragma unroll
+  for (int r = 1; r < kWays; ++r) {
+    sum = __dadd_rn(sum, part[0][r][lane]);
+    all &= flags[r][lane];
+  }
+  finite = (all & 1) != 0;
+  // a column whose draws are all equal has that value as its mean, whatever the sum of N copies rounds to
+  const double mean = (all & 2) ? first : __ddiv_rn(sum, Nd);
+
+  double p2 = 0.0, p4 = 0.0;
+  if (live) {
+    for (int i = way; i < N; i += kWays) {
+      const double c = __dsub_rn(draw(xq, A, i), mean), c2 = __dmul_rn(c, c);
+      csq[(int64_t)i * Q + q] = finite ? c2 : NAN;
+      p2 = __dadd_rn(p2, c2);
+      p4 = __dadd_rn(p4, __dmul_rn(c2, c2));
+    }
+  }
+  part[1][way][lane] = p2;
+  part[2][way][lane] = p4;
+  __syncthreads();
+  if (way != 0 || !live) return;
+  double s2 = part[1][0][lane], s4 = part[2][0][lane];
+#pragma unroll
+  for (int r = 1; r < kWays; ++r) {
+    s2 = __dadd_rn(s2, part[1][r][lane]);
+    s4 = __dadd_rn(s4, part[2][r][lane]);
+  }
+  const double m2 = __ddiv_rn(s2, Nd), m4 = __ddiv_rn(s4, Nd);
+  mean_out[q] = finite ? plus_zero(mean) : NAN;
+  m2_out[q] = finite ? m2 : NAN;
+  m4_out[q] = finite ? m4 : NAN;
+  sd_out[q] = finite ? sqrt(__ddiv_rn(__dmul_rn(m2, Nd), __dsub_rn(Nd, 1.0))) : NAN;
+}
+
+// q_p from rows lo, hi of the sorted array: rankdiag::quantile_kernel's arithmetic (numpy's lerp, from the nearer
+// neighbour), every operation rounded once
+__global__ __launch_bounds__(kThreads) void quantile_kernel(const double* __restrict__ sorted, int lo, int hi,
+                                                            double frac, int64_t Q, double* __restrict__ out) {
+  const int64_t q = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (q >= Q) return;
+  const double a = sorted[(int64_t)lo * Q + q], b = sorted[(int64_t)hi * Q + q];
+  const double d = __dsub_rn(b, a);
+  out[q] = frac >= 0.5 ? __dsub_rn(b, __dmul_rn(d, __dsub_rn(1.0, frac))) : __dadd_rn(a, __dmul_rn(d, frac));
+}
+
+__global__ __launch_bounds__(kThreads) void hdi_kernel(const double* __restrict__ sorted, int N, int k, int64_t Q,
+                                                       double* __restrict__ lower, double* __restrict__ upper) {
+  const int64_t q = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (q >= Q) return;
+  const double* __restrict__ col = sorted + q;
+  int best = 0;
+  double width = __dsub_rn(col[(int64_t)k * Q], col[0]);
+  for (int i = 1; i + k < N; ++i) {
+    const double w = __dsub_rn(col[(int64_t)(i + k) * Q], col[(int64_t)i * Q]);
+    if (w < width) {                              // strict: the first window that attains the minimum
+      width = w;
+      best = i;
+    }
+  }
+  lower[q] = col[(int64_t)best * Q];              // NaN rows (a non-finite draw) compare false throughout: NaN, NaN
+  upper[q] = col[(int64_t)(best + k) * Q];
+}
+
+// ess_mean is read and, for a column without variance (m2 = 0), overwritten with NaN: the per-sequence means of
+// sgmcmc_chain_ess may round away from a constant column's value and leave it a variance at rounding level
+__global__ __launch_bounds__(kThreads) void mcse_kernel(const double* __restrict__ sd, const double* __restrict__ m2,
+                                                        const double* __restrict__ m4, double* __restrict__ ess_mean,
+                                                        const double* __restrict__ ess_sd, int64_t Q,
+                                                        double* __restrict__ mcse_mean, double* __restrict__ mcse_sd) {
+  const int64_t q = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (q >= Q) return;
+  const double v2 = m2[q], v4 = m4[q];
+  const bool varies = v2 > 0.0;                   // false for NaN as well
+  const double em = varies ? ess_mean[q] : NAN, es = varies ? ess_sd[q] : NAN;
+  ess_mean[q] = em;
+  mcse_mean[q] = __ddiv_rn(sd[q], sqrt(em));
+  const double excess = __dsub_rn(v4, __dmul_rn(v2, v2));
+  mcse_sd[q] = sqrt(__ddiv_rn(__ddiv_rn(__ddiv_rn(excess, es), v2), 4.0));
+}
+
+// ---- the regularised incomplete beta function I_x(a, b) and its inverse, fp64 -------------------------------------------
+// I_x(a, b) = front(x) cf(x; a, b) / a for x < (a + 1) / (a + b + 2), else 1 - front(x) cf(1 - x; b, a) / b, with
+// front(x) = x^a (1 - x)^b / B(a, b) and cf the continued fraction 26.5.8 of Abramowitz and Stegun by the modified Lentz
+// recurrence.  The accuracy of I at a, b of 10^4 is that of log front: lgamma(a + b) - lgamma(a) - lgamma(b) loses
+// log10(a log a) digits, so Stirling's formula is applied to the three of them on paper and only its remainders D are
+// evaluated (TOMS 708's brcomp),
+//   log front = a l(u) + b l(w) + log(a b / (2 pi T)) / 2 + D(T) - D(a) - D(b),   l(u) = log1p(u) - u,
+//   T = a + b,  u = (x T - a) / a,  w = -(x T - a) / b   (a u + b w = 0 exactly: the first-order terms cancel on paper),
+//   D(z) = lgamma(z) - ((z - 1/2) log z - z + log(2 pi) / 2) = 1/(12 z) - 1/(360 z^3) + ...: the series from
+//   z = kStirling on, the difference itself below (where lgamma is small and the difference costs nothing),
+// and T carried as the rounded sum and its rounding error so that x T - a is formed with one rounding.
+
+constexpr double kStirling = 20.0;
+constexpr int kFractionTerms = 4000;
+constexpr int kRootSteps = 200;
+
+__device__ __forceinline__ double stirling_rest(double z) {
+  if (z < kStirling) return lgamma(z) - ((z - 0.5) * log(z) - z + 0.91893853320467274178);
+  const double r = 1.0 / z, r2 = r * r;
+  return r * (1.0 / 12.0 - r2 * (1.0 / 360.0 - r2 * (1.0 / 1260.0 - r2 * (1.0 / 1680.0 - r2 * (1.0 / 1188.0 - r2 * (691.0 / 360360.0))))));
+}
+
+// log1p(u) - u, u > -1: for |u| <= 0.5 as -r u + 2 r^3 (1/3 + r^2/5 + r^4/7 + ...), r = u / (2 + u), which has no
+// cancellation (-r u is the whole second-order term)
+__device__ __forceinline__ double log1p_minus(double u) {
+  if (fabs(u) > 0.5) return log1p(u) - u;
+  const double r = u / (2.0 + u), r2 = r * r;
+  double power = 1.0, series = 1.0 / 3.0;
+  for (int k = 5; k < 80; k += 2) {
+    power *= r2;
+    const double term = power / (double)k;
+    series += term;
+    if (term < 1e-18 * series) break;
+  }
+  return 2.0 * r * r2 * series - r * u;
+}
+
+struct Beta {               // a, b and what does not depend on x
+  double a, b, total, total_err, log_const;
+};
+
+__device__ __forceinline__ Beta make_beta(double a, double b) {
+  Beta B;
+  B.a = a;
+  B.b = b;
+  B.total = a + b;
+  const double bv = B.total - a;                                  // two-sum: total + total_err = a + b exactly
+  B.total_err = (a - (B.total - bv)) + (b - bv);
+  B.log_const = 0.5 * log(a * b / (6.283185307179586477 * B.total)) + stirling_rest(B.total) - stirling_rest(a) -
+                stirling_rest(b);
+  return B;
+}
+
+// x^a (1 - x)^b / B(a, b), 0 < x < 1
+__device__ __forceinline__ double beta_front(const Beta& B, double x) {
+  const double excess = fma(x, B.total, -B.a) + x * B.total_err;      // x T - a
+  const double u = excess / B.a, w = -excess / B.b;
+  if (!(u > -1.0 && w > -1.0)) return 0.0;
+  return exp(B.a * log1p_minus(u) + B.b * log1p_minus(w) + B.log_const);
+}
+
+__device__ double beta_fraction(double a, double b, double x) {
+  constexpr double tiny = 1e-300;
+  const double qab = a + b, qap = a + 1.0, qam = a - 1.0;
+  double c = 1.0, d = 1.0 - qab * x / qap;
+  if (fabs(d) < tiny) d = tiny;
+  d = 1.0 / d;
+  double h = d;
+  for (int m = 1; m <= kFractionTerms; ++m) {
+    const double m2 = 2.0 * m;
+    double aa = m * (b - m) * x / ((qam + m2) * (a + m2));
+    d = 1.0 + aa * d;
+    if (fabs(d) < tiny) d = tiny;
+    c = 1.0 + aa / c;
+    if (fabs(c) < tiny) c = tiny;
+    d = 1.0 / d;
+    h *= d * c;
+    aa = -(a + m) * (qab + m) * x / ((a + m2) * (qap + m2));
+    d = 1.0 + aa * d;
+    if (fabs(d) < tiny) d = tiny;
+    c = 1.0 + aa / c;
+    if (fabs(c) < tiny) c = tiny;
+    d = 1.0 / d;
+    const double del = d * c;
+    h *= del;
+    if (fabs(del - 1.0) <= 2.3e-16) break;
+  }
+  return h;
+}
+
+// I_x(a, b) and the density x^(a-1) (1 - x)^(b-1) / B(a, b), 0 < x < 1
+__device__ double beta_cdf(const Beta& B, double x, double* density) {
+  const double front = beta_front(B, x);
+  *density = front / (x * (1.0 - x));
+  if (x < (B.a + 1.0) / (B.total + 2.0)) return front * beta_fraction(B.a, B.b, x) / B.a;
+  return 1.0 - front * beta_fraction(B.b, B.a, 1.0 - x) / B.b;
+}
+
+// the x in (0, 1) with I_x(a, b) = P, 0 < P < 1, a, b > 0: Newton steps kept inside a bracket that every evaluation
+// narrows (a bisection step whenever Newton leaves it or the density vanishes).
+// It starts `sds` standard deviations of the beta distribution from its mean (the normal approximation of the root:
+// P = Phi(sds)) and ends with the first Newton step below 1e-10 x: its successor would be about 1e-20 x C with
+// C = |f''| x / (2 f'), which is x / sd <= sqrt(a + b) that close to the mean -- far below an ulp.
+__device__ double beta_inverse(const Beta& B, double P, double sds) {
+  const double mean = B.a / B.total;
+  double lo = 0.0, hi = 1.0, x = mean + sds * sqrt(mean * (B.b / B.total) / (B.total + 1.0));
+  if (!(x > lo && x < hi)) x = mean;
+  for (int it = 0; it < kRootSteps; ++it) {
+    double density;
+    const double f = beta_cdf(B, x, &density) - P;
+    if (f == 0.0) return x;
+    if (f < 0.0) lo = x;
+    else hi = x;
+    double next = x - f / density;
+    if (next == x) break;                                              // a Newton step below half an ulp
+    const bool newton = next > lo && next < hi;
+    if (!newton) next = 0.5 * (lo + hi);
+    if (next == lo || next == hi) break;                               // the bracket has no interior left
+    const bool last = newton && fabs(next - x) <= 1e-10 * x;
+    x = next;
+    if (last) break;
+  }
+  return x;
+}
+
+__global__ __launch_bounds__(kThreads) void mcse_quantile_kernel(const double* __restrict__ sorted, int N, double p,
+                                                                 const double* __restrict__ ess_q, int64_t Q,
+                                                                 double* __restrict__ mcse, double* __restrict__ a_out,
+                                                                 double* __restrict__ b_out, int32_t* __restrict__ lo_out,
+                                                                 int32_t* __restrict__ hi_out) {
+  const int64_t q = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (q >= Q) return;
+  const double ess = ess_q[q], Nd = (double)N;
+  double a = NAN, b = NAN, value = NAN;
+  int lo = -1, hi = -1;
+  if (ess > 0.0 && ess < INFINITY) {
+    const double alpha = __dadd_rn(__dmul_rn(ess, p), 1.0), beta = __dadd_rn(__dmul_rn(ess, __dsub_rn(1.0, p)), 1.0);
+    const Beta B = make_beta(alpha, beta);                             // alpha, beta >= 1 and finite
+    a = beta_inverse(B, kLowerTail, -1.0);
+    b = beta_inverse(B, kUpperTail, 1.0);
+    if (a == a && b == b) {
+      const double fl = floor(__dmul_rn(a, Nd)), ce = ceil(__dmul_rn(b, Nd));
+      lo = min(max((int)fmax(fl, 1.0) - 1, 0), N - 1);                 // in range whatever the root search returned
+      hi = min(max((int)fmin(ce, Nd) - 1, 0), N - 1);
+      value = __ddiv_rn(__dsub_rn(sorted[(int64_t)hi * Q + q], sorted[(int64_t)lo * Q + q]), 2.0);
+    }
+  }
+  mcse[q] = value;
+  if (a_out) a_out[q] = a;
+  if (b_out) b_out[q] = b;
+  if (lo_out) lo_out[q] = lo;
+  if (hi_out) hi_out[q] = hi;
+}
+
+inline bool grid_of(int64_t quantities, int per_block, dim3* grid) {
+  const int64_t blocks = (quantities + per_block - 1) / per_block;
+  if (blocks > 0x7fffffffll) return false;
+  *grid = dim3((unsigned)blocks);
+  return true;
+}
+
+}  // namespace summary
+
+extern "C" int sgmcmc_summary_tile_quantities(int total_draws) { return summary::tile_quantities(total_draws); }
+
+extern "C" int sgmcmc_summary_sort(const void* x, int is_f64, int64_t chain_stride, int64_t draw_stride, int chains,
+                                   int draws, int64_t quantities, int split, double* sorted, void* stream) {
+  SGMCMC_FRESH_ERROR_STATE();
+  diag::Seqs A;
+  if (!x || !sorted || !summary::make_seqs(chain_stride, draw_stride, chains, draws, quantities, split, &A))
+    return (int)hipErrorInvalidValue;
+  const int N = A.J * A.n, n_pad = summary::padded(N), tq = summary::tile_quantities(N);
+  int log_tq = 0;
+  while ((1 << log_tq) < tq) ++log_tq;
+  dim3 grid;
+  if (!summary::grid_of(quantities, tq, &grid)) return (int)hipErrorInvalidValue;
+  static bool attr_done = false;
+  if (!attr_done) {       // above 64 KiB of LDS per workgroup has to be asked for
+    const int most = (int)((size_t)summary::kMaxDraws * sizeof(double) + summary::kMaxTile * sizeof(int));
+    for (const void* k : {reinterpret_cast<const void*>(summary::sort_kernel<float>),
+                          reinterpret_cast<const void*>(summary::sort_kernel<double>)}) {
+      const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, most);
+      if (e != hipSuccess) return (int)e;
+    }
+    attr_done = true;
+  }
+  const size_t lds = (size_t)n_pad * tq * sizeof(double) + (size_t)tq * sizeof(int);
+  const dim3 block(summary::kSortThreads);
+  if (is_f64) SGMCMC_LAUNCH(summary::sort_kernel<double>, grid, block, lds, (hipStream_t)stream, (const double*)x, A,
+                            quantities, N, n_pad, log_tq, sorted);
+  else SGMCMC_LAUNCH(summary::sort_kernel<float>, grid, block, lds, (hipStream_t)stream, (const float*)x, A,
+                     quantities, N, n_pad, log_tq, sorted);
+  return (int)hipGetLastError();
+}
+
+extern "C" int sgmcmc_summary_moments(const void* x, int is_f64, int64_t chain_stride, int64_t draw_stride, int chains,
+                                      int draws, int64_t quantities, int split, double* mean, double* sd, double* m2,
+                                      double* m4, double* csq, void* stream) {
+  SGMCMC_FRESH_ERROR_STATE();
+  diag::Seqs A;
+  dim3 grid;
+  if (!x || !mean || !sd || !m2 || !m4 || !csq ||
+      !summary::make_seqs(chain_stride, draw_stride, chains, draws, quantities, split, &A) ||
+      !summary::grid_of(quantities, summary::kMomentTile, &grid))
+    return (int)hipErrorInvalidValue;
+  const dim3 block(summary::kThreads);
+  if (is_f64) SGMCMC_LAUNCH(summary::moments_kernel<double>, grid, block, 0, (hipStream_t)stream, (const double*)x, A,
+                            quantities, mean, sd, m2, m4, csq);
+  else SGMCMC_LAUNCH(summary::moments_kernel<float>, grid, block, 0, (hipStream_t)stream, (const float*)x, A,
+                     quantities, mean, sd, m2, m4, csq);
+  return (int)hipGetLastError();
+}
+
+extern "C" int sgmcmc_summary_quantile(const double* sorted, int chains, int draws, int split, double prob,
+                                       int64_t quantities, double* out, void* stream) {
+  SGMCMC_FRESH_ERROR_STATE();
+  diag::Seqs A;
+  rankdiag::Stats S;
+  dim3 grid;
+  if (!sorted || !out || !summary::make_seqs(0, 0, chains, draws, quantities, split, &A) ||
+      !rankdiag::make_stats(&prob, 1, A.J * A.n, &S) || !summary::grid_of(quantities, summary::kThreads, &grid))
+    return (int)hipErrorInvalidValue;
+  SGMCMC_LAUNCH(summary::quantile_kernel, grid, dim3(summary::kThreads), 0, (hipStream_t)stream, sorted, S.lo[0],
+                S.hi[0], S.frac[0], quantities, out);
+  return (int)hipGetLastError();
+}
+
+extern "C" int sgmcmc_summary_hdi(const double* sorted, int chains, int draws, int split, double mass,
+                                  int64_t quantities, double* lower, double* upper, void* stream) {
+  SGMCMC_FRESH_ERROR_STATE();
+  diag::Seqs A;
+  dim3 grid;
+  if (!sorted || !lower || !upper || !(mass > 0.0 && mass < 1.0) ||
+      !summary::make_seqs(0, 0, chains, draws, quantities, split, &A) ||
+      !summary::grid_of(quantities, summary::kThreads, &grid))
+    return (int)hipErrorInvalidValue;
+  const int N = A.J * A.n, k = (int)floor(mass * (double)N);
+  if (k < 1 || k > N - 1) return (int)hipErrorInvalidValue;
+  SGMCMC_LAUNCH(summary::hdi_kernel, grid, dim3(summary::kThreads), 0, (hipStream_t)stream, sorted, N, k, quantities,
+                lower, upper);
+  return (int)hipGetLastError();
+}
+
+extern "C" int sgmcmc_summary_mcse(const double* sd, const double* m2, const double* m4, double* ess_mean,
+                                   const double* ess_sd, int64_t quantities, double* mcse_mean, double* mcse_sd,
+                                   void* stream) {
+  SGMCMC_FRESH_ERROR_STATE();
+  dim3 grid;
+  if (!sd || !m2 || !m4 || !ess_mean || !ess_sd || !mcse_mean || !mcse_sd || quantities <= 0 ||
+      !summary::grid_of(quantities, summary::kThreads, &grid))
+    return (int)hipErrorInvalidValue;
+  SGMCMC_LAUNCH(summary::mcse_kernel, grid, dim3(summary::kThreads), 0, (hipStream_t)stream, sd, m2, m4, ess_mean,
+                ess_sd, quantities, mcse_mean, mcse_sd);
+  return (int)hipGetLastError();
+}
+
+extern "C" int sgmcmc_summary_mcse_quantile(const double* sorted, int chains, int draws, int split, double prob,
+                                            const double* ess_q, int64_t quantities, double* mcse, double* a, double* b,
+                                            int32_t* lo, int32_t* hi, void* stream) {
+  SGMCMC_FRESH_ERROR_STATE();
+  diag::Seqs A;
+  dim3 grid;
+  if (!sorted || !ess_q || !mcse || !(prob > 0.0 && prob < 1.0) ||
+      !summary::make_seqs(0, 0, chains, draws, quantities, split, &A) ||
+      !summary::grid_of(quantities, summary::kThreads, &grid))
+    return (int)hipErrorInvalidValue;
+  SGMCMC_LAUNCH(summary::mcse_quantile_kernel, grid, dim3(summary::kThreads), 0, (hipStream_t)stream, sorted,
+                A.J * A.n, prob, ess_q, quantities, mcse, a, b, lo, hi);
+  return (int)hipGetLastError();
+}

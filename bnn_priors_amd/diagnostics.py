@@ -19,7 +19,9 @@ import torch
 
 from . import _hip
 
-__all__ = ("split_rhat", "ess", "rhat_ess", "rank_rhat_ess", "weight_space", "function_space", "summary")
+__all__ = ("split_rhat", "ess", "rhat_ess", "rank_rhat_ess", "weight_space", "function_space", "summary",
+           "posterior_summary", "weight_space_summary", "function_space_summary", "summary_tile", "PosteriorSummary",
+           "PosteriorSummaryParts")
 
 MAX_SEQ = _hip.DIAG_MAX_SEQ          # draws per sequence (n)
 MAX_CHAINS = _hip.DIAG_MAX_CHAINS    # sequences (J): 2 M with split
@@ -28,12 +30,22 @@ TILE = _hip.DIAG_TILE                # quantities per workgroup of the ESS kerne
 RANK_CHUNK = 64                      # rank_rhat_ess walks the quantities in multiples of the score kernel's 64 lanes
 RANK_DRAW_BYTES = 16                 # workspace per draw and quantity: z (fp64) and the two indicators (fp32)
 RANK_QUANTITY_BYTES = 72             # ... and per quantity: six order statistics and three quantiles (fp64)
+SUMMARY_MAX_DRAWS = _hip.SUMMARY_MAX_DRAWS   # draws (N = J n) that posterior_summary's column sort takes
+SUMMARY_CHUNK = 64                   # posterior_summary walks the quantities in multiples of the widest sort tile
+SUMMARY_DRAW_BYTES = 16              # workspace per draw and quantity: the sorted column (fp64) and c^2 (fp64), whose
+#                                      place the two indicators (fp32) take once its ESS is out
+SUMMARY_QUANTITY_BYTES = 0           # ... and per quantity: nothing, every result is written where it is returned
 SKIP_KEYS = ("steps", "timestamps")
 
 RankDiagnostics = collections.namedtuple("RankDiagnostics", "rhat ess_bulk ess_tail")
 RankDiagnosticsParts = collections.namedtuple(
     "RankDiagnosticsParts", RankDiagnostics._fields + ("rhat_bulk", "rhat_folded", "ess_lower", "ess_upper", "median",
                                                        "q_lower", "q_upper"))
+PosteriorSummary = collections.namedtuple(
+    "PosteriorSummary", "mean sd mcse_mean mcse_sd ess_mean ess_sd quantiles mcse_quantile ess_quantile hdi_lower "
+                        "hdi_upper")
+PosteriorSummaryParts = collections.namedtuple("PosteriorSummaryParts",
+                                               PosteriorSummary._fields + ("m2", "m4", "a", "b", "lo", "hi"))
 
 
 def _check(x, split, device=True):
@@ -186,20 +198,125 @@ def rank_rhat_ess(x, split=True, tail_probs=(0.05, 0.95), workspace_bytes=256 <<
     return RankDiagnosticsParts(*out) if parts else RankDiagnostics(*out[:3])
 
 
+def summary_tile(N):
+    """TQ, the quantities that one workgroup of the column sort stages at N draws (``sgmcmc_summary_tile_quantities``
+    restated): the most columns of N_pad fp64, N_pad the next power of two, that fit 128 KiB, at most 64"""
+    if not 4 <= N <= SUMMARY_MAX_DRAWS:
+        raise ValueError(f"N = {N} is outside [4, {SUMMARY_MAX_DRAWS}]")
+    return min(SUMMARY_MAX_DRAWS // max(4, 1 << (N - 1).bit_length()), _hip.SUMMARY_MAX_TILE)
+
+
+def _check_summary(x, split, probs, hdi_prob, workspace_bytes):
+    "-> (M, S, shape, Q, probs, hdi_prob, quantities per chunk) of a valid posterior_summary call; ValueError otherwise"
+    M, S, shape, Q = _check(x, split, device=False)
+    try:
+        probs = tuple(float(p) for p in probs)
+    except (TypeError, ValueError):
+        raise ValueError("probs must be a sequence of probabilities") from None
+    if not all(0.0 < p < 1.0 for p in probs):
+        raise ValueError(f"probs must lie inside (0, 1), not {probs!r}")
+    try:
+        hdi_prob = float(hdi_prob)
+    except (TypeError, ValueError):
+        raise ValueError("hdi_prob must be a probability") from None
+    if not 0.0 < hdi_prob < 1.0:
+        raise ValueError(f"hdi_prob must lie inside (0, 1), not {hdi_prob!r}")
+    n, J = (S // 2, 2 * M) if split else (S, M)
+    N = J * n
+    if N > SUMMARY_MAX_DRAWS:
+        raise ValueError(f"{J} sequences of {n} draws are {N} draws: at most {SUMMARY_MAX_DRAWS} are supported")
+    if not 1 <= math.floor(hdi_prob * N) <= N - 1:
+        raise ValueError(f"hdi_prob = {hdi_prob!r} covers none of the {N} draws")
+    per_quantity = SUMMARY_DRAW_BYTES * N + SUMMARY_QUANTITY_BYTES
+    chunk = int(workspace_bytes) // per_quantity // SUMMARY_CHUNK * SUMMARY_CHUNK
+    if chunk < SUMMARY_CHUNK:
+        raise ValueError(f"workspace_bytes = {workspace_bytes} is too small: {SUMMARY_CHUNK} quantities of {N} draws "
+                         f"need {SUMMARY_CHUNK * per_quantity} bytes")
+    _check(x, split)
+    return M, S, shape, Q, probs, hdi_prob, chunk
+
+
+def posterior_summary(x, probs=(0.05, 0.5, 0.95), hdi_prob=0.94, split=True, workspace_bytes=256 << 20, parts=False):
+    """x [M, S, *shape] (CUDA, fp32 or fp64) -> ``PosteriorSummary``: what the posterior of every quantity is and how
+    precisely the M S stored draws pin it down, as ``include/sgmcmc_hip.h`` defines it (Vehtari et al. 2021; the R package
+    posterior; ArviZ's unimodal HDI).  ``mean``, ``sd``, their Monte Carlo standard errors ``mcse_mean``, ``mcse_sd`` and
+    the effective sample sizes behind those, ``ess_mean``, ``ess_sd``, each [*shape]; ``quantiles``, ``mcse_quantile``
+    and ``ess_quantile``, each [P, *shape], for the P probabilities ``probs``; ``hdi_lower``, ``hdi_upper``: the
+    narrowest interval that holds ``hdi_prob`` of the draws.  All fp64.  Next to ``rhat_ess`` / ``rank_rhat_ess`` this
+    is the usual summary table; whether two priors differ by more than the sampler's noise is a question about
+    ``mcse_mean``.
+
+    ``parts=True``: a ``PosteriorSummaryParts`` that also carries ``m2``, ``m4`` (the central moments), ``a``, ``b``
+    (the beta quantiles behind ``mcse_quantile``, [P, *shape]) and ``lo``, ``hi`` (its two ranks, int32, [P, *shape]).
+    ``split`` chooses the sequences of the effective sample sizes as in ``rhat_ess`` (with an odd S a chain's middle
+    draw enters nothing).  The columns are sorted by an LDS sorting network, so at most 16384 draws enter.  The
+    quantities are walked in chunks (multiples of 64) whose sorted columns and scratch fit ``workspace_bytes``: one
+    workspace per call, 16 bytes per draw and quantity; the chunking changes no bit.  A quantity with a non-finite draw
+    gives NaN in everything; a constant one its mean and quantiles, ``sd`` = 0 and NaN for every ess and mcse.
+    Everything stays on the current stream."""
+    split = bool(split)
+    M, S, shape, Q, probs, hdi_prob, chunk = _check_summary(x, split, probs, hdi_prob, workspace_bytes)
+    dev = x.device
+    n, J = (S // 2, 2 * M) if split else (S, M)
+    N, P = J * n, len(probs)
+    res = torch.empty((10 + 5 * P, Q), dtype=torch.float64, device=dev)
+    ranks = torch.empty((2 * P, Q), dtype=torch.int32, device=dev)
+    if Q:
+        if not x[0, 0].is_contiguous():
+            x = x.contiguous()
+        chunk = min(chunk, (Q + SUMMARY_CHUNK - 1) // SUMMARY_CHUNK * SUMMARY_CHUNK)
+        work = torch.empty(chunk * (SUMMARY_DRAW_BYTES * N + SUMMARY_QUANTITY_BYTES) // 8, dtype=torch.float64,
+                           device=dev)
+        item, is_f64 = x.element_size(), int(x.dtype == torch.float64)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream().cuda_stream
+            L = _hip.lib()
+
+            def run(name, *args):
+                _hip.check(getattr(L, name)(*args, stream), name)
+
+            for q0 in range(0, Q, chunk):
+                Qc = min(chunk, Q - q0)
+                ordered = work.data_ptr()                                     # [N][Qc] fp64: the sorted columns
+                csq = ordered + 8 * N * Qc                                    # [J][n][Qc] fp64: c^2, and after its ESS ...
+                ind = (csq, csq + 4 * N * Qc)                                 # ... [J][n][Qc] fp32 twice: two indicators
+                seqs = (x.data_ptr() + q0 * item, is_f64, x.stride(0), x.stride(1), M, S, Qc, int(split))
+                mean, sd, mcse_mean, mcse_sd, ess_mean, ess_sd, hdi_lower, hdi_upper, m2, m4 = (
+                    res[r].data_ptr() + 8 * q0 for r in range(10))
+                quant, mcse_q, ess_q, a, b = ([res[10 + g * P + k].data_ptr() + 8 * q0 for k in range(P)]
+                                              for g in range(5))
+                lo, hi = ([ranks[g * P + k].data_ptr() + 4 * q0 for k in range(P)] for g in range(2))
+                shape_args = (M, S, int(split))
+                run("sgmcmc_summary_sort", *seqs, ordered)
+                run("sgmcmc_summary_moments", *seqs, mean, sd, m2, m4, csq)
+                run("sgmcmc_chain_ess", *seqs, ess_mean, None, None)
+                run("sgmcmc_chain_ess", csq, 1, n * Qc, Qc, J, n, Qc, 0, ess_sd, None, None)
+                run("sgmcmc_summary_mcse", sd, m2, m4, ess_mean, ess_sd, Qc, mcse_mean, mcse_sd)
+                run("sgmcmc_summary_hdi", ordered, *shape_args, hdi_prob, Qc, hdi_lower, hdi_upper)
+                for k in range(P):
+                    run("sgmcmc_summary_quantile", ordered, *shape_args, probs[k], Qc, quant[k])
+                for k in range(0, P, 2):                                      # the indicators of two thresholds at once
+                    k2 = min(k + 1, P - 1)
+                    run("sgmcmc_chain_tail_indicators", *seqs, quant[k], quant[k2], *ind)
+                    for kk, src in ((k, ind[0]), (k2, ind[1]))[:k2 - k + 1]:
+                        run("sgmcmc_chain_ess", src, 0, n * Qc, Qc, J, n, Qc, 0, ess_q[kk], None, None)
+                for k in range(P):
+                    run("sgmcmc_summary_mcse_quantile", ordered, *shape_args, probs[k], ess_q[k], Qc, mcse_q[k], a[k],
+                        b[k], lo[k], hi[k])
+    one = [t.reshape(shape) for t in res[:10]]
+    many = [res[10 + g * P:10 + (g + 1) * P].reshape((P,) + shape) for g in range(5)]
+    lo, hi = (ranks[g * P:(g + 1) * P].reshape((P,) + shape) for g in range(2))
+    out = one[:6] + many[:3] + one[6:8]
+    return PosteriorSummaryParts(*out, one[8], one[9], many[3], many[4], lo, hi) if parts else PosteriorSummary(*out)
+
+
 def _diagnosable(name, v):
     return (name not in SKIP_KEYS and isinstance(v, torch.Tensor) and v.is_floating_point()
             and not name.endswith("num_batches_tracked"))
 
 
-def weight_space(samples, chains=None, split=True, rank_normalised=False):
-    """R-hat and ESS of every stored weight: ``{name: (rhat, ess)}``, each shaped like the weight; with
-    ``rank_normalised=True`` ``{name: rank_rhat_ess(...)}``, the ``(rhat, ess_bulk, ess_tail)`` that heavy-tailed
-    weights need.
-
-    ``samples``: a list of per-chain sample dicts (``runner.get_samples()``: name -> [S, ...]), stacked chain by chain;
-    or ONE dict in ``evaluation.gather_samples``' layout (name -> [M S, ...], chain by chain) with ``chains=M``, viewed
-    as [M, S, ...] without a copy.  The bookkeeping keys (``steps``, ``timestamps``), integer tensors and the BatchNorm
-    counters are skipped."""
+def _stacked(samples, chains):
+    "``weight_space``' input -> {name: [M, S, ...]} of the tensors that are diagnosed; ValueError for a malformed one"
     if isinstance(samples, dict):
         if chains is None or int(chains) < 1:
             raise ValueError("one dict of gathered samples needs chains=M")
@@ -224,6 +341,19 @@ def weight_space(samples, chains=None, split=True, rank_normalised=False):
             if any(not isinstance(v, torch.Tensor) or v.shape != vs[0].shape or v.dtype != vs[0].dtype for v in vs):
                 raise ValueError(f"{name}: the chains' samples differ in shape or dtype")
             stacked[name] = torch.stack(vs)
+    return stacked
+
+
+def weight_space(samples, chains=None, split=True, rank_normalised=False):
+    """R-hat and ESS of every stored weight: ``{name: (rhat, ess)}``, each shaped like the weight; with
+    ``rank_normalised=True`` ``{name: rank_rhat_ess(...)}``, the ``(rhat, ess_bulk, ess_tail)`` that heavy-tailed
+    weights need.
+
+    ``samples``: a list of per-chain sample dicts (``runner.get_samples()``: name -> [S, ...]), stacked chain by chain;
+    or ONE dict in ``evaluation.gather_samples``' layout (name -> [M S, ...], chain by chain) with ``chains=M``, viewed
+    as [M, S, ...] without a copy.  The bookkeeping keys (``steps``, ``timestamps``), integer tensors and the BatchNorm
+    counters are skipped."""
+    stacked = _stacked(samples, chains)
     for name, v in stacked.items():
         _check(v, bool(split))                   # every tensor is checked before the first launch
     if rank_normalised:
@@ -235,13 +365,36 @@ def function_space(tables, split=True, rank_normalised=False):
     """``tables``: a list of per-chain ``acc`` [S, N, C] (``evaluation.predictive_tables``: normalised
     log-probabilities per sample) -> (R-hat, ESS) of the predictive probabilities ``exp(acc)``, each [N, C]; with
     ``rank_normalised=True`` their ``rank_rhat_ess``: ``(rhat, ess_bulk, ess_tail)``."""
+    tables = _tables(tables)
+    if rank_normalised:
+        return rank_rhat_ess(torch.stack(tables).exp(), split)
+    return rhat_ess(torch.stack(tables).exp(), split)
+
+
+def _tables(tables):
     tables = list(tables)
     if not tables or any(not isinstance(a, torch.Tensor) or a.dim() != 3 or a.shape != tables[0].shape
                          or a.dtype != tables[0].dtype for a in tables):
         raise ValueError("tables must be a non-empty list of [S, N, C] tensors of one shape and dtype")
-    if rank_normalised:
-        return rank_rhat_ess(torch.stack(tables).exp(), split)
-    return rhat_ess(torch.stack(tables).exp(), split)
+    return tables
+
+
+def weight_space_summary(samples, chains=None, split=True, **kw):
+    """``posterior_summary`` of every stored weight: ``{name: PosteriorSummary}``, every field shaped like the weight
+    (the per-probability ones with a leading P).  ``samples`` and ``chains`` are ``weight_space``'s, with the same skips;
+    ``kw`` goes to ``posterior_summary`` (``probs``, ``hdi_prob``, ``workspace_bytes``, ``parts``)."""
+    stacked = _stacked(samples, chains)
+    args = (kw.get("probs", (0.05, 0.5, 0.95)), kw.get("hdi_prob", 0.94), kw.get("workspace_bytes", 256 << 20))
+    for name, v in stacked.items():
+        _check_summary(v, bool(split), *args)    # every tensor is checked before the first launch
+    return {name: posterior_summary(v, split=split, **kw) for name, v in stacked.items()}
+
+
+def function_space_summary(tables, split=True, **kw):
+    """``tables``: a list of per-chain ``acc`` [S, N, C] (``evaluation.predictive_tables``) -> the ``posterior_summary``
+    of the predictive probabilities ``exp(acc)``, every field [N, C] (or [P, N, C]).  Its ``mean`` is the ensemble's
+    predictive probability, its ``mcse_mean`` how well the S draws per chain determine that probability."""
+    return posterior_summary(torch.stack(_tables(tables)).exp(), split=split, **kw)
 
 
 def summary(rhat, ess, ess_tail=None):

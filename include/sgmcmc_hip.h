@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGMCMC_ABI_VERSION 19
+#define SGMCMC_ABI_VERSION 20
 #define SGMCMC_CHUNK 4096 /* default elements per arena chunk = 256 threads x 4 items x 4 elements */
 #define SGMCMC_CHUNK_SMALL 1024 /* small models: one item per thread, 4x more workgroups */
 #define SGMCMC_NSUMS 6
@@ -1118,6 +1118,80 @@ int sgmcmc_chain_quantiles(const double* ostat, int chains, int draws, int split
 int sgmcmc_chain_tail_indicators(const void* x, int is_f64, int64_t chain_stride, int64_t draw_stride, int chains,
                                  int draws, int64_t quantities, int split, const double* q_lower,
                                  const double* q_upper, float* lower, float* upper, void* stream);
+
+/* ---- Posterior summaries with Monte Carlo standard errors (fp64, deterministic) ---------------------------------------
+ * What the posterior is and how precisely the stored draws pin it down: mean, sd, quantiles, the highest-density
+ * interval, and the Monte Carlo standard error (MCSE) of the mean, the sd and every quantile.  The reference has no such
+ * function; this is the definition (Vehtari, Gelman, Simpson, Carpenter, Buerkner 2021; the R package posterior's
+ * mcse_mean, mcse_sd, mcse_quantile; ArviZ's unimodal HDI), restated in tests/summary_reference.py.  x, split, n, J, the
+ * sequences and N = J n are as in the rank-normalised section; v_1 .. v_N are the draws that enter the sequences, in
+ * sequence order (draw i = j n + s; with split and an odd count a chain's middle draw enters nothing), v_(k) the k-th
+ * smallest counted from 0; fp32 is widened on load and all arithmetic is fp64; every operation is rounded once (nothing
+ * is contracted into an fma); -0.0 counts as, and is written as, +0.0.  Ess(.) is sgmcmc_chain_ess applied to J
+ * sequences of n values (for v itself: to x with the call's split).
+ *   sums           every sum over the draws runs over i = 0 .. N-1 as SGMCMC_DIAG_MEAN_WAYS interleaved partial sums
+ *                  (i = r mod SGMCMC_DIAG_MEAN_WAYS, each in ascending i, from +0.0) added in ascending r: an order fixed
+ *                  by (chains, draws, split)
+ *   mean           sum_i v_i / N; a column whose draws are all equal has that value as its mean (the sum of N copies may
+ *                  round away from it)
+ *   moments        c_i = v_i - mean, m2 = sum_i c_i^2 / N, m4 = sum_i (c_i^2)^2 / N
+ *   sd             sqrt(m2 N / (N - 1))
+ *   ess_mean       Ess(v);   mcse_mean = sd / sqrt(ess_mean)
+ *   ess_sd         Ess(c^2); mcse_sd = sqrt((m4 - m2 m2) / ess_sd / m2 / 4)   (posterior::mcse_sd, kurtosis-aware)
+ *   quantile q_p   any p in (0, 1): the type-7 definition of the rank-normalised section in numpy's operation order,
+ *                  read from the sorted column; bit-equal to sgmcmc_chain_quantiles
+ *   mcse_quantile  ess_q(p) = Ess(1[v <= q_p]); alpha = ess_q p + 1, beta = ess_q (1 - p) + 1;
+ *                  a = I^-1(0.1586553; alpha, beta), b = I^-1(0.8413447; alpha, beta), I^-1 the inverse of the
+ *                  regularised incomplete beta function x -> I_x(alpha, beta);
+ *                  lo = max(floor(a N), 1) - 1, hi = min(ceil(b N), N) - 1; mcse_q(p) = (v_(hi) - v_(lo)) / 2
+ *   HDI of mass h  k = floor(h N) (1 <= k <= N - 1 is required), w_i = v_(i+k) - v_(i) for i = 0 .. N-k-1, i* the first
+ *                  i that attains the minimum; the interval is (v_(i*), v_(i*+k))
+ *   NaN rule       a quantity with a non-finite draw gives NaN in everything (lo = hi = -1).  A quantity with m2 = 0 (a
+ *                  constant column) gives its mean and quantiles, sd = 0, HDI bounds equal to the value, and NaN for
+ *                  every ess and mcse.  A constant indicator (W = 0 in its Ess) gives NaN for that ess_q and mcse_q
+ *                  (a = b = NaN, lo = hi = -1).
+ * a and b are the only results that are not fixed to the bit by this text: I^-1 is evaluated on the device by a bracketed
+ * Newton search on I_x (a continued fraction; the beta function through the remainders of Stirling's formula, which
+ * keeps a relative error of a few 10^-15 at alpha, beta of 10^4), and lo, hi and mcse_q inherit a difference only where
+ * a N or b N lies within that error of an integer.
+ * The caller provides every buffer; nothing is allocated, nothing synchronises, everything runs on the given stream; no
+ * atomics; a quantity's result depends on its own column only, whatever the grid, the tile or the chunk.  Limits: those
+ * of sgmcmc_chain_ess and N <= SGMCMC_SUMMARY_MAX_DRAWS; anything else, a NULL required pointer or a probability
+ * outside (0, 1) returns hipErrorInvalidValue and launches nothing. */
+#define SGMCMC_SUMMARY_MAX_DRAWS 16384 /* N: one fp64 column of the sort's LDS tile (128 KiB) */
+#define SGMCMC_SUMMARY_MAX_TILE 64     /* quantities per workgroup of the sort, at most */
+
+/* TQ, the quantities per workgroup of sgmcmc_summary_sort at N = total_draws: the most columns of N_pad fp64 (N_pad the
+ * next power of two, at least 4) that fit 128 KiB, SGMCMC_SUMMARY_MAX_TILE at most; 0 for an N that is refused.  Host
+ * arithmetic only. */
+int sgmcmc_summary_tile_quantities(int total_draws);
+/* sorted [N][quantities] (fp64, contiguous): every column's draws in ascending order, zeros as +0.0; a column with a
+ * non-finite draw is NaN throughout.  One launch: a workgroup stages an [N_pad][TQ] tile in LDS, pads it with +inf
+ * after deciding the non-finite rule, and sorts its columns with a bitonic network, O(N log^2 N) per column. */
+int sgmcmc_summary_sort(const void* x, int is_f64, int64_t chain_stride, int64_t draw_stride, int chains, int draws,
+                        int64_t quantities, int split, double* sorted, void* stream);
+/* mean, sd, m2, m4 [quantities] and csq [J][n][quantities] (fp64, contiguous) = c^2, the input of ess_sd (NaN for a
+ * quantity with a non-finite draw).  One launch, lane = quantity and one thread group per partial sum, the data read
+ * twice. */
+int sgmcmc_summary_moments(const void* x, int is_f64, int64_t chain_stride, int64_t draw_stride, int chains, int draws,
+                           int64_t quantities, int split, double* mean, double* sd, double* m2, double* m4,
+                           double* csq, void* stream);
+/* out [quantities]: q_prob from `sorted` as sgmcmc_summary_sort wrote it for the same (chains, draws, split). */
+int sgmcmc_summary_quantile(const double* sorted, int chains, int draws, int split, double prob, int64_t quantities,
+                            double* out, void* stream);
+/* lower, upper [quantities]: the HDI of `mass` from `sorted`. */
+int sgmcmc_summary_hdi(const double* sorted, int chains, int draws, int split, double mass, int64_t quantities,
+                       double* lower, double* upper, void* stream);
+/* mcse_mean, mcse_sd [quantities] from sd, m2, m4 (sgmcmc_summary_moments), ess_mean = Ess(v) and ess_sd = Ess(c^2);
+ * ess_mean is also WRITTEN: NaN where m2 = 0 (the per-sequence means inside Ess may leave a constant column a variance
+ * at rounding level). */
+int sgmcmc_summary_mcse(const double* sd, const double* m2, const double* m4, double* ess_mean, const double* ess_sd,
+                        int64_t quantities, double* mcse_mean, double* mcse_sd, void* stream);
+/* mcse [quantities]: mcse_q(prob) from `sorted` and ess_q [quantities] = Ess(1[v <= q_prob]); a, b [quantities] (fp64)
+ * and lo, hi [quantities] (int32) receive the parts and may each be NULL. */
+int sgmcmc_summary_mcse_quantile(const double* sorted, int chains, int draws, int split, double prob,
+                                 const double* ess_q, int64_t quantities, double* mcse, double* a, double* b,
+                                 int32_t* lo, int32_t* hi, void* stream);
 
 /* ---- Model comparison: PSIS-LOO with Pareto-k and WAIC (fp64, deterministic) -------------------------------------------
  * Vehtari, Gelman, Gabry 2017; Vehtari, Simpson, Gelman, Yao, Gabry 2024; Watanabe 2010; the generalised Pareto fit of
