@@ -586,14 +586,20 @@ __device__ __forceinline__ void step_body(const sgmcmc_layout& L, const sgmcmc_s
       float z[4] = {0.f, 0.f, 0.f, 0.f};
       if (draw_noise) spec_normal4(A.seed, A.stream, A.draw, 0u, (noise0 + (uint64_t)j) >> 2, z);
       Item<T> mn, tn, vn;
+      if (WITH_PRIOR) {
+#pragma unroll
+        for (int l = 0; l < 4; ++l) g[it].x[l] = PC.template apply<false>(g[it].x[l], th[it].x[l], calc_logp, lp, dls_unused);
+      }
+      // p.grad holds the full gradient afterwards.  PRIOR: as sgmcmc_prior_grad leaves it, i.e. BEFORE the clamp (which
+      // the launch after sgmcmc_prior_grad applies in flight without writing g back); PARTS: the clamped one
+      if (PRIOR && !PARTS) store_item<T>(gp + j, g[it]);
 #pragma unroll
       for (int l = 0; l < 4; ++l) {
-        if (WITH_PRIOR) g[it].x[l] = PC.template apply<false>(g[it].x[l], th[it].x[l], calc_logp, lp, dls_unused);
         if (C.do_clamp) g[it].x[l] = clamp_grad<T>(g[it].x[l], C.clampv);
         update_elem<T, KIND>(C, (T)z[l], g[it].x[l], m[it].x[l], th[it].x[l], v[it].x[l], mn.x[l],
                              tn.x[l], vn.x[l], acc);
       }
-      if (WITH_PRIOR) store_item<T>(gp + j, g[it]);  // p.grad holds the full gradient afterwards
+      if (PARTS) store_item<T>(gp + j, g[it]);
       if (save) {
         store_item<T>(pth + j, th[it]);
         store_item<T>(pg + j, g[it]);
@@ -618,16 +624,21 @@ __device__ __forceinline__ void step_body(const sgmcmc_layout& L, const sgmcmc_s
       float z[4] = {0.f, 0.f, 0.f, 0.f};
       if (draw_noise) spec_normal4(A.seed, A.stream, A.draw, 0u, (noise0 + (uint64_t)j) >> 2, z);
       Item<T> mn, tn, vn;
+      if (WITH_PRIOR) {
+#pragma unroll
+        for (int l = 0; l < 4; ++l)
+          if (l < n) g.x[l] = PC.template apply<false>(g.x[l], th.x[l], calc_logp, lp, dls_unused);
+      }
+      if (PRIOR && !PARTS) store_guarded<T>(gp + j, g, n);   // (before the clamp, see the vector path)
 #pragma unroll
       for (int l = 0; l < 4; ++l) {
         if (l < n) {
-          if (WITH_PRIOR) g.x[l] = PC.template apply<false>(g.x[l], th.x[l], calc_logp, lp, dls_unused);
           if (C.do_clamp) g.x[l] = clamp_grad<T>(g.x[l], C.clampv);
           update_elem<T, KIND>(C, (T)z[l], g.x[l], m.x[l], th.x[l], v.x[l], mn.x[l], tn.x[l],
                                vn.x[l], acc);
         }
       }
-      if (WITH_PRIOR) store_guarded<T>(gp + j, g, n);
+      if (PARTS) store_guarded<T>(gp + j, g, n);
       if (save) {
         store_guarded<T>(pth + j, th, n);
         store_guarded<T>(pg + j, g, n);
@@ -1064,14 +1075,28 @@ __global__ __launch_bounds__(kThreads) void finalize_dot_kernel(sgmcmc_layout L,
 // d/dtheta of -log p(theta)/N and (optionally) log p(theta), element-wise families with scalar
 // loc/scale/df (SURVEY.md Appendix A "Priors").  The gradient is applied in the working precision
 // with one rounding for the factor and one fma into g; log p is evaluated and accumulated in fp64.
+// lgamma(a + 1/2) - lgamma(a) for a >= 32 without forming either term: each is ~a log a, so their rounded difference
+// loses log2(a log a) bits (df = 1e6: 5e-10 absolute on a normaliser of ~7).  Stirling's series of both, subtracted
+// term by term: a log1p(1/(2a)) + (log a - 1)/2 + sum_k c_k (b^-(2k-1) - a^-(2k-1)), b = a + 1/2; the first omitted
+// term is below 3e-17 at a = 32.
+__device__ __forceinline__ double lgamma_half_step(double a) {
+  const double b = a + 0.5, ia = 1.0 / a, ib = 1.0 / b, ia2 = ia * ia, ib2 = ib * ib;
+  const double series = (ib - ia) * (1.0 / 12.0) - (ib * ib2 - ia * ia2) * (1.0 / 360.0) +
+                        (ib * ib2 * ib2 - ia * ia2 * ia2) * (1.0 / 1260.0) -
+                        (ib * ib2 * ib2 * ib2 - ia * ia2 * ia2 * ia2) * (1.0 / 1680.0);
+  return a * log1p(0.5 * ia) + 0.5 * (log(a) - 1.0) + series;
+}
+
 __device__ __forceinline__ double prior_log_norm(const sgmcmc_segment& s, double scale) {
   // per-element normalising constant of the density; the hyper-prior kinds
   // accumulate their full log-density element by element and need none
   if (s.prior_kind == SGMCMC_PRIOR_NORMAL) return -log(scale) - 0.9189385332046727418;
   if (s.prior_kind == SGMCMC_PRIOR_LAPLACE) return -log(2.0 * scale);
-  if (s.prior_kind == SGMCMC_PRIOR_STUDENT_T)
-    return -log(scale) - 0.5 * log(s.prior_df) - 0.5723649429247000870 -
-           lgamma(0.5 * s.prior_df) + lgamma(0.5 * (s.prior_df + 1.0));
+  if (s.prior_kind == SGMCMC_PRIOR_STUDENT_T) {
+    const double head = -log(scale) - 0.5 * log(s.prior_df) - 0.5723649429247000870;
+    if (s.prior_df >= 64.0) return head + lgamma_half_step(0.5 * s.prior_df);
+    return head - lgamma(0.5 * s.prior_df) + lgamma(0.5 * (s.prior_df + 1.0));   // (df < 64: the arithmetic as it has always been)
+  }
   if (s.prior_kind == SGMCMC_PRIOR_CAUCHY) return -log(scale) - 1.1447298858494001741;  // -ln(pi sigma)
   if (s.prior_kind == SGMCMC_PRIOR_GENNORM) return -log(2.0 * scale) - lgamma(1.0 / s.prior_df) + log(s.prior_df);
   return 0.0;

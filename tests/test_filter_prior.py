@@ -137,13 +137,19 @@ def _autograd(pr):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("chunk", [_hip.CHUNK, _hip.CHUNK_SMALL])
-def test_filters_straddling_chunks_match_float64_autograd(chunk):
+@pytest.mark.parametrize("chunk,dtype", [(_hip.CHUNK, torch.float64), (_hip.CHUNK_SMALL, torch.float64),
+                                         (_hip.CHUNK, torch.float32), (_hip.CHUNK_SMALL, torch.float32)],
+                         ids=["4096", "1024", "4096-float32", "1024-float32"])
+def test_filters_straddling_chunks_match_float64_autograd(chunk, dtype):
     """several segments whose filters straddle the chunk boundaries (9, 25, 3 do not divide 4096 / 1024) and 1 x 1
-    filters, Normal and generalised-normal bases, float64: the kernel's gradient and log-density against autograd"""
+    filters, Normal and generalised-normal bases: the kernel's gradient and log-density against float64 autograd.
+    float32 arenas: the kernel works in fp64 from the stored values and rounds once into g, so the reference is float64
+    autograd at the WIDENED float32 parameters (and widened arguments) and the gradient is held to one rounding of the
+    result with a safety factor of 2, 2 * 2^-24 |ref|, plus the allowance the float64 comparison gives autograd itself"""
+    import copy
     from bnn_priors_amd import mcmc
     dev, N = "cuda:0", 37.0
-    torch.set_default_dtype(torch.float64)
+    torch.set_default_dtype(dtype)
     try:
         torch.manual_seed(3)
         priors = [P.ConvCorrelatedNormal((64, 64, 3, 3), 0., 0.3, lengthscale=0.7),
@@ -155,18 +161,27 @@ def test_filters_straddling_chunks_match_float64_autograd(chunk):
     model = torch.nn.ModuleList(priors).to(dev)
     want_lp, want_g = 0.0, []
     for pr in priors:
-        lp, g = _autograd(pr)
+        lp, g = _autograd(pr if dtype == torch.float64 else copy.deepcopy(pr).double())
         want_lp += lp
         want_g.append(g)
     opt = mcmc.VerletSGLD([pr.p for pr in priors], lr=0.01, num_data=N, momentum=0.9, chunk_elems=chunk)
-    assert opt.engine.chunk == chunk
+    assert opt.engine.chunk == chunk and opt.engine.dtype == dtype
     assert opt.fuse_priors(model) == []
-    g0 = [torch.randn(pr.p.shape, dtype=torch.float64, generator=torch.Generator().manual_seed(i)) for i, pr in enumerate(priors)]
+    g0 = [torch.randn(pr.p.shape, dtype=dtype, generator=torch.Generator().manual_seed(i)).double()
+          for i, pr in enumerate(priors)]
     for pr, g in zip(priors, g0):
-        pr.p.grad = g.to(dev)
+        pr.p.grad = g.to(dtype).to(dev)
     opt.add_prior_gradient(calc_log_prior=True)
     for pr, g, w in zip(priors, g0, want_g):
-        torch.testing.assert_close(pr.p.grad.cpu(), g - w / N, rtol=1e-10, atol=1e-12)
+        ref = g - w / N
+        if dtype == torch.float64:
+            torch.testing.assert_close(pr.p.grad.cpu(), ref, rtol=1e-10, atol=1e-12)
+        else:
+            err = (pr.p.grad.cpu().double() - ref).abs()
+            bound = 2 * 2.0 ** -24 * ref.abs() + (1e-10 * ref.abs() + 1e-12)
+            worst = (err / bound).max().item()
+            print(f"filter-ratio {tuple(pr.p.shape)} chunk {chunk}: worst error / bound {worst:.4f}")
+            assert worst <= 1.0, (tuple(pr.p.shape), worst)
     assert opt.fused_log_prior().item() == pytest.approx(want_lp, rel=1e-11, abs=1e-9)
 
 
