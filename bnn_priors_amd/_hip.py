@@ -24,7 +24,7 @@ INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 SOURCES = [os.path.join(_HERE, "csrc", "sgmcmc_hip.hip")]
 SOURCE = SOURCES[0]
 
-ABI_VERSION = 20
+ABI_VERSION = 21
 CHUNK = 4096
 CHUNK_SMALL = 1024
 NSUMS = 6
@@ -184,6 +184,9 @@ PSIS_MIN_DRAWS, PSIS_MAX_DRAWS, PSIS_MAX_TAIL, PSIS_OWN, PSIS_POINTWISE, PSIS_TO
 WEIGHTS_SLICE, WEIGHTS_MAX_MODELS, WEIGHTS_STATE, WEIGHTS_NOISE_PURPOSE = 1024, 32, 72, 4
 GMIX_TILE, GMIX_MAX_SAMPLES, GMIX_MAX_QUANTILES, PIT_MAX_LEVELS = 128, 32768, 64, 1024
 FIT_TILE_DOUBLES, FIT_TILE_ROWS, FIT_MAX_BLOCKS, FIT_PART, FIT_STATE = 5120, 512, 1024, 408, 1288
+GOF_MAX_RECORDS, GOF_MAX_QUANTILES, GOF_TILE, GOF_MAX_BLOCKS, GOF_PART, GOF_OUT = 6, 4096, 1024, 1024, 8, 8
+GOF_UNIFORM, GOF_NORM, GOF_LAPLACE, GOF_T, GOF_GENNORM, GOF_DGAMMA = 0, 1, 2, 3, 4, 5
+GOF_DF_RANGE, GOF_BETA_RANGE, GOF_A_RANGE = (0.1, 1e4), (0.1, 10.0), (0.1, 1e4)
 
 
 class FitGeometry(ctypes.Structure):
@@ -191,6 +194,12 @@ class FitGeometry(ctypes.Structure):
     _fields_ = [("P", ctypes.c_int32), ("F", ctypes.c_int32), ("f_major", ctypes.c_int32), ("reserved", ctypes.c_int32),
                 ("events", ctypes.c_int64), ("size", ctypes.c_int64 * 4), ("stride", ctypes.c_int64 * 4),
                 ("f_stride", ctypes.c_int64), ("pos", ctypes.c_int64 * FILTER_MAX_P)]
+
+
+class GofRecord(ctypes.Structure):
+    "sgmcmc_gof_record"
+    _fields_ = [("family", ctypes.c_int32), ("reserved", ctypes.c_int32), ("shape", ctypes.c_double),
+                ("loc", ctypes.c_double), ("scale", ctypes.c_double)]
 
 
 EXPORTS = {
@@ -422,6 +431,13 @@ EXPORTS = {
                                               ctypes.c_int64] + [ctypes.c_double] * 3 + [ctypes.c_void_p] * 5),
     "sgmcmc_fit_abs_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(FitGeometry), ctypes.c_double,
                                             ctypes.c_double] + [ctypes.c_void_p] * 5),
+    "sgmcmc_gof_workspace_doubles": (ctypes.c_int64, [ctypes.c_int64]),
+    "sgmcmc_gof_cdf": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(GofRecord),
+                                      ctypes.c_void_p, ctypes.c_void_p]),
+    "sgmcmc_gof_statistics": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(GofRecord),
+                                             ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "sgmcmc_gof_ppf": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(GofRecord),
+                                      ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "sgmcmc_debug_normals": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                             ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64,
                                             ctypes.c_uint32, ctypes.c_void_p]),

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGMCMC_ABI_VERSION 20
+#define SGMCMC_ABI_VERSION 21
 #define SGMCMC_CHUNK 4096 /* default elements per arena chunk = 256 threads x 4 items x 4 elements */
 #define SGMCMC_CHUNK_SMALL 1024 /* small models: one item per thread, 4x more workgroups */
 #define SGMCMC_NSUMS 6
@@ -1397,6 +1397,81 @@ int sgmcmc_fit_mvt_iterate(const void* w, int dtype, const sgmcmc_fit_geometry* 
 /* Definition 3: out [5], zeros [1].  Two launches. */
 int sgmcmc_fit_abs_stats(const void* w, int dtype, const sgmcmc_fit_geometry* geometry, double loc, double beta,
                          double* part, int64_t* counts, double* out, int64_t* zeros, void* stream);
+
+/* ---- Goodness of fit of the fitted element-wise families (fp64, deterministic) ------------------------------------------
+ * The question the fits of sgmcmc_fit_* were made for: which family the weights follow, and where a family fails.
+ * This is the definition, restated in tests/gof_reference.py.
+ * A RECORD is (family, shape, loc, scale), the parameters in scipy's order:
+ *     SGMCMC_GOF_UNIFORM  on [loc, loc + scale]        (no shape)     the identity, which makes the sums testable exactly
+ *     SGMCMC_GOF_NORM, SGMCMC_GOF_LAPLACE               (no shape)
+ *     SGMCMC_GOF_T        shape = df    in [SGMCMC_GOF_DF_MIN, SGMCMC_GOF_DF_MAX]
+ *     SGMCMC_GOF_GENNORM  shape = beta  in [SGMCMC_GOF_BETA_MIN, SGMCMC_GOF_BETA_MAX]
+ *     SGMCMC_GOF_DGAMMA   shape = a     in [SGMCMC_GOF_A_MIN, SGMCMC_GOF_A_MAX]
+ * loc finite, scale finite and > 0.  All arithmetic is fp64.
+ *  1. The log-tail.  z = |x - loc| / scale; lt(z) = log T(z), T the probability beyond z on one side, formed in log space:
+ *       norm     log(erfcx(z / sqrt 2) / 2) - z^2 / 2                laplace  log(1/2) - z
+ *       t        T = I_x(df/2, 1/2) / 2, x = df / (df + z^2), I the regularised incomplete beta function by its
+ *                continued fraction (of whichever tail converges; the upper tail's in its even part, written in x, 1 - x
+ *                and (df + 1) (1 - x) / 2 - 1/2, each formed from z with one rounding), its prefactor x^(df/2)
+ *                (1 - x)^(1/2) / B(df/2, 1/2) a logarithm in which only Stirling's remainders of the three lgamma appear
+ *       gennorm  T = Q(1/beta, z^beta) / 2                           dgamma   T = Q(a, z) / 2
+ *     Q(a, y) the regularised upper incomplete gamma function: 1 - P by P's series for y < a + 1, the continued fraction
+ *     (modified Lentz) else; the prefactor y^a e^-y / Gamma(a) a logarithm, written a (log1p(u) - u) + log(a / 2 pi) / 2
+ *     - D(a), u = (y - a) / a, D Stirling's remainder of lgamma(a).  z = 0 gives T = 1/2 exactly.  On the side of x:
+ *     x > loc: 1 - F = T, log(1 - F) = lt, F = 1 - T, log F = log1p(-T); x < loc: the mirror image.  lt is finite where
+ *     T underflows (lt down to about -1e300).  uniform: F = clamp((x - loc) / scale, 0, 1), log F = log(F),
+ *     log(1 - F) = log1p(-F).  |z| >= 1e150 is taken as T = 0; a NaN gives NaN.
+ *  2. The statistics of an ASCENDING array x_(1) <= ... <= x_(n) under a record, u_i = F(x_(i)):
+ *       D+ = max_i (i / n - u_i)     D- = max_i (u_i - (i - 1) / n)     D = max(D+, D-), attained at the smallest such i
+ *       (D+ where D+ >= D-);  W^2 = 1 / (12 n) + sum_i (u_i - (2 i - 1) / (2 n))^2;
+ *       A^2 = -n - (1 / n) sum_i [(2 i - 1) log F_i + (2 (n - i) + 1) log(1 - F_i)]
+ *     (the Anderson-Darling sum with its second factor re-indexed i -> n + 1 - i).  Summation order: tiles of
+ *     SGMCMC_GOF_TILE consecutive values; workgroup b of min(tiles, SGMCMC_GOF_MAX_BLOCKS) takes tiles b, b + blocks, ...;
+ *     thread t of 256 adds values t, t + 256, ... of each of its tiles in ascending order (compensated, Neumaier), the
+ *     threads meet in the fixed tree t += t + 128, ..., t + 1 and the workgroups in ascending order (compensated).  A
+ *     function of the sorted values and the records only.  Non-finite values are counted and left out.
+ *     out, SGMCMC_GOF_OUT doubles per record: D, D+, D-, the 1-based index of the supremum, x there, W^2, A^2, the count
+ *     of non-finite values.  A^2 is +inf when a value lies where a record's F is 0 or 1.
+ *  3. Quantiles at p_j = (j - 1/2) / K, j = 1 .. K <= SGMCMC_GOF_MAX_QUANTILES: model [count][K], F^-1(p_j) = loc -+ scale z
+ *     with lt(z) = log min(p, 1 - p) by Newton steps on lt kept inside a bracket, until a step is below 1e-10 z;
+ *     empirical [K], numpy's linear rule on the ascending array: pos = (n - 1) p, lo = floor(pos), g = pos - lo,
+ *     a = x[lo], b = x[min(lo + 1, n - 1)]; b - (b - a) (1 - g) for g >= 1/2, a + (b - a) g else, every operation rounded once.
+ * 1 <= n <= 2^31 - 1, 1 <= count <= SGMCMC_GOF_MAX_RECORDS; anything else, a NULL pointer or a parameter outside its
+ * range returns hipErrorInvalidValue and launches nothing.  Nothing is allocated, nothing synchronises. */
+#define SGMCMC_GOF_MAX_RECORDS 6
+#define SGMCMC_GOF_MAX_QUANTILES 4096
+#define SGMCMC_GOF_TILE 1024
+#define SGMCMC_GOF_MAX_BLOCKS 1024
+#define SGMCMC_GOF_PART 8
+#define SGMCMC_GOF_OUT 8
+#define SGMCMC_GOF_UNIFORM 0
+#define SGMCMC_GOF_NORM 1
+#define SGMCMC_GOF_LAPLACE 2
+#define SGMCMC_GOF_T 3
+#define SGMCMC_GOF_GENNORM 4
+#define SGMCMC_GOF_DGAMMA 5
+#define SGMCMC_GOF_DF_MIN 0.1
+#define SGMCMC_GOF_DF_MAX 1e4
+#define SGMCMC_GOF_BETA_MIN 0.1
+#define SGMCMC_GOF_BETA_MAX 10.0
+#define SGMCMC_GOF_A_MIN 0.1
+#define SGMCMC_GOF_A_MAX 1e4
+typedef struct sgmcmc_gof_record {
+  int32_t family, reserved;
+  double shape, loc, scale;
+} sgmcmc_gof_record;
+
+/* Doubles of the workspace of sgmcmc_gof_statistics at n values; -1 for an n that is refused.  Host only. */
+int64_t sgmcmc_gof_workspace_doubles(int64_t n);
+/* Definition 1 at m points x (fp32 or fp64): out [4][m] = F, 1 - F, log F, log(1 - F).  One launch. */
+int sgmcmc_gof_cdf(const void* x, int is_f64, int64_t m, const sgmcmc_gof_record* record, double* out, void* stream);
+/* Definition 2 for `count` records at once: one pass in which every value is loaded once, and one workgroup that adds
+ * the partials.  out [count][SGMCMC_GOF_OUT]. */
+int sgmcmc_gof_statistics(const void* sorted, int is_f64, int64_t n, const sgmcmc_gof_record* records, int count,
+                          double* workspace, double* out, void* stream);
+/* Definition 3: model [count][K], empirical [K].  One launch. */
+int sgmcmc_gof_ppf(const void* sorted, int is_f64, int64_t n, const sgmcmc_gof_record* records, int count, int K,
+                   double* model, double* empirical, void* stream);
 
 /* Test hook: out[i] = spec normal (fp32) of noise index start+i. */
 int sgmcmc_debug_normals(float* out, int64_t start, int64_t n, uint64_t seed, uint32_t stream,
