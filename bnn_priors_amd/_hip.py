@@ -24,7 +24,7 @@ INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 SOURCES = [os.path.join(_HERE, "csrc", "sgmcmc_hip.hip")]
 SOURCE = SOURCES[0]
 
-ABI_VERSION = 21
+ABI_VERSION = 22
 CHUNK = 4096
 CHUNK_SMALL = 1024
 NSUMS = 6
@@ -41,6 +41,8 @@ PRIOR_GAMMA_SOFTPLUS, PRIOR_UNIFORM_CDF, PRIOR_HALFCAUCHY_SOFTPLUS, PRIOR_IMPROP
 PRIOR_FILTER_WHITENED, PRIOR_MULTIVARIATE_T = 10, 11
 PRIOR_HAS_LINKS, PRIOR_FULL, PRIOR_EVENTS = 1, 2, 4
 RIDE_JOBS = 4
+FRAG_JOBS = 24
+FRAG_LDS, FRAG_REG = 1, 2       # `form` of sgmcmc_conv3x3_wfrag_fwd / _bwd
 FILTER_MAX_P = 25
 FILTER_BASE_NORMAL, FILTER_BASE_GENNORM, FILTER_BASE_LAPLACE, FILTER_BASE_DOUBLE_GAMMA = 0, 1, 2, 3
 
@@ -447,6 +449,14 @@ EXPORTS = {
     "sgmcmc_conv3x3_frag_fwd": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 2),
     "sgmcmc_conv3x3_frag_bwd": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.POINTER(ConvBwdEpilogue)]
                                 + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_int), ctypes.c_void_p]),
+    "sgmcmc_conv3x3_wfrag_fwd": (ctypes.c_int, [ctypes.c_void_p] * 3 + [ctypes.c_int] * 3
+                                 + [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "sgmcmc_conv3x3_wfrag_bwd": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.POINTER(ConvBwdEpilogue)]
+                                 + [ctypes.c_void_p] * 2 + [ctypes.c_int] * 3
+                                 + [ctypes.POINTER(ctypes.c_int), ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                    ctypes.c_void_p]),
+    "sgmcmc_conv_stem_fwd_frags": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+                                                                          ctypes.c_int, ctypes.c_void_p]),
 }
 
 # include/sgmcmc_hip_alternatives.h (libsgmcmc_hip_alt.so only)

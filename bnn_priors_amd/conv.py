@@ -97,20 +97,65 @@ def _frag_entry(w):
     return e
 
 
-def _prepare(weights):
-    "fragments of all ``weights`` in one launch (sgmcmc_conv3x3_prepare_weights splits beyond SGMCMC_FRAG_JOBS)"
+def _frag_jobs(weights):
     jobs = (_hip.FragJob * len(weights))()
     for j, w in zip(jobs, weights):
         e = _frag_entry(w)
         j.w, j.fwd, j.dgrad, j.channels = w.data_ptr(), e[1].data_ptr(), e[2].data_ptr(), w.shape[0]
-    err = _hip.lib().sgmcmc_conv3x3_prepare_weights(ctypes.cast(jobs, ctypes.c_void_p), len(weights), _stream())
+    return jobs
+
+
+def _prepare(weights):
+    "fragments of all ``weights`` in one launch (sgmcmc_conv3x3_prepare_weights splits beyond SGMCMC_FRAG_JOBS)"
+    err = _hip.lib().sgmcmc_conv3x3_prepare_weights(ctypes.cast(_frag_jobs(weights), ctypes.c_void_p), len(weights),
+                                                    _stream())
     if err:
         _hip.check(err, "sgmcmc_conv3x3_prepare_weights")
+
+
+# ---- the DEFAULT kernels on those fragments (csrc/conv_hip.inc, FRAG; sgmcmc_conv3x3_wfrag_fwd / _bwd) ---------------
+# Every workgroup of a trunk convolution's forward and data gradient used to permute the raw [co][ci][3][3] weights into
+# its MFMA operands; on this route it reads the fragments, prepared once per gradient evaluation -- same registers, same
+# MFMA order, the same bits (tests/test_conv_weight_frags.py).  The preparation costs no launch: ``deferring(owner)``
+# QUEUES the jobs of the owner's known weights and the stem's forward, the first launch of the evaluation, which reads
+# no trunk weight, takes the queue along in trailing workgroups (``take_frag_jobs``; sgmcmc_conv_stem_fwd_frags).
+# ``frags(w)`` never depends on that: a job still queued (no stem ran first) is flushed with the rest of the queue by one
+# ``_prepare`` launch, an unknown weight (a model's first scope) gets its own.  Outside a scope nothing is known about
+# a weight's history and a launch per convolution would be needed: the raw-weight kernels run there.
+# ``WEIGHT_FRAGS`` = {(channels, side): roles}, roles a subset of {"fwd", "dgrad"}: module attributes, not environment
+# switches; empty restores the raw-weight route everywhere; ``WEIGHT_FRAG_FORM`` = {(channels, side, role): form}: how
+# a workgroup fetches its fragments (_hip.FRAG_LDS: linear 16-byte copy to LDS + ds_read_b128; _hip.FRAG_REG: 16-byte
+# global loads into the registers); ``FRAG_JOBS_FIRST`` puts the carried jobs' workgroups ahead of the stem's own instead
+# of behind them.  The shipped values are the measured ones (docs/lab_notes.md, profiles/weight_frags_ab.txt).
+WEIGHT_FRAGS = {(16, 32): {"dgrad"}, (32, 16): {"fwd"}, (64, 8): {"fwd", "dgrad"}}
+WEIGHT_FRAG_FORM = {(16, 32, "fwd"): _hip.FRAG_REG, (16, 32, "dgrad"): _hip.FRAG_REG,
+                    (32, 16, "fwd"): _hip.FRAG_LDS, (32, 16, "dgrad"): _hip.FRAG_REG,
+                    (64, 8, "fwd"): _hip.FRAG_LDS, (64, 8, "dgrad"): _hip.FRAG_REG}
+FRAG_JOBS_FIRST = False
+_frag_queue = {}      # id(weight) -> weight: the active scope's fragment jobs that wait for a carrier
+
+
+def weight_frags(c, hw, role):
+    "does ``role`` (\"fwd\" / \"dgrad\") of the (c, hw) trunk convolution read prepared fragments here?"
+    return _defer["active"] and role in WEIGHT_FRAGS.get((c, hw), ())
+
+
+def take_frag_jobs(device):
+    "the queued weights (at most _hip.FRAG_JOBS) whose fragments the launch about to be enqueued prepares -> list"
+    taken = [w for w in _frag_queue.values() if w.device == device][:_hip.FRAG_JOBS]
+    for w in taken:
+        del _frag_queue[id(w)]
+    return taken
 
 
 def frags(w):
     "(forward fragments, data-gradient fragments) of the contiguous [C, C, 3, 3] float32 weight w, current"
     e = _frag_entry(w)
+    if id(w) in _frag_queue:        # no carrier ran first: one launch for everything that is still queued
+        queued = list(_frag_queue.values())
+        _frag_queue.clear()
+        _prepare(queued)
+        _frag_valid.update(id(q) for q in queued)
     if id(w) not in _frag_valid:
         _prepare([w])
         if _defer["active"]:
@@ -236,9 +281,12 @@ def deferring(owner=None):
     _fx_reset(owner)
     _frag_valid.clear()
     _pending.clear()                # leftovers of a pass that raised before its final callback
-    if (PERSISTENT or PERSISTENT_BWD) and owner is not None:
+    _frag_queue.clear()
+    if (PERSISTENT or PERSISTENT_BWD or WEIGHT_FRAGS) and owner is not None:
         known = [w for w in (r() for r in _owner_weights.get(id(owner), ())) if w is not None and w.is_cuda]
-        if known:
+        if known and WEIGHT_FRAGS:      # no launch here: the stem's forward carries the jobs (or ``frags`` flushes them)
+            _frag_queue.update((id(w), w) for w in known)
+        elif known:
             _prepare(known)
             _frag_valid.update(id(w) for w in known)
     try:
@@ -255,6 +303,7 @@ def deferring(owner=None):
         _defer["weights"] = {}
         _fx_reset(None)
         _frag_valid.clear()
+        _frag_queue.clear()
     _flush_pending()                # no-op when the backward's final callback already ran
 
 
@@ -309,11 +358,27 @@ def _run(x, w, transpose_w, want_stats=False):
     if want_stats:   # [channels][slices][2] partial (sum, centred sum of squares) of y, for the BatchNorm that follows
         slices = lib.sgmcmc_conv3x3_stat_slices(x.shape[0], x.shape[1], x.shape[2])
         stats = torch.empty((x.shape[1], slices, 2), dtype=torch.float64, device=x.device)
+        if not transpose_w:
+            err = forward_stats(lib, x, w, y, stats, _stream())
+            if err:
+                _hip.check(err, "sgmcmc_conv3x3")
+            return y, stats
     err = lib.sgmcmc_conv3x3(x.data_ptr(), w.data_ptr(), y.data_ptr(), x.shape[0], x.shape[1], x.shape[2],
                              int(transpose_w), 0 if stats is None else stats.data_ptr(), _stream())
     if err:
         _hip.check(err, "sgmcmc_conv3x3")
     return y, stats
+
+
+def forward_stats(lib, x, w, y, stats, s):
+    """y, stats <- conv3x3(x, w) with its statistics slices by the default kernel -- THE forward of the step's trunk
+    convolutions, for the layered operator (``_run``) and the fused residual block (resblock.py) alike: on prepared
+    fragments where ``WEIGHT_FRAGS`` says so, else on the raw weights (same bits) -> the error code"""
+    n, c, hw = x.shape[0], x.shape[1], x.shape[2]
+    if weight_frags(c, hw, "fwd"):
+        return lib.sgmcmc_conv3x3_wfrag_fwd(x.data_ptr(), frags(w)[0].data_ptr(), y.data_ptr(), n, c, hw, stats.data_ptr(),
+                                            WEIGHT_FRAG_FORM[(c, hw, "fwd")], s)
+    return lib.sgmcmc_conv3x3(x.data_ptr(), w.data_ptr(), y.data_ptr(), n, c, hw, 0, stats.data_ptr(), s)
 
 
 def _weight_grad(x, dy, w=None):
@@ -432,8 +497,10 @@ def trunk_backward(lib, x, w, dy, s, add=None, sums_for=None, G=1):
         # the weight-gradient slabs leave the critical path: side stream, joined before the pass's slab reduction
         split_backward(lib, x, w, dy, dx, E, part, S.count)
     else:
-        # (slab reductions pending from earlier launches of this pass ride in this one: take_riders)
-        err = bwd_ex(lib, x, w, dy, dx, E, None, part, S.count, s, take_riders(c, hw))
+        # (slab reductions pending from earlier launches of this pass ride in this one: take_riders); the data-gradient
+        # role on prepared fragments for the step's own variants: the sums epilogue, one minibatch (WEIGHT_FRAGS)
+        frag = frags(w)[1] if (weight_frags(c, hw, "dgrad") and sums_for is not None and G == 1) else None
+        err = bwd_ex(lib, x, w, dy, dx, E, None, part, S.count, s, take_riders(c, hw), frag)
         if err:
             _hip.check(err, "sgmcmc_conv3x3_bwd_ex")
     return dx, S.finish(part, torch.empty_like(w), 9), partial, n_partials
@@ -481,16 +548,20 @@ def _fill_jobs(jobs, entries):
     return jobs
 
 
-def bwd_ex(lib, x, w, dy, dx, E, dw, scratch, slabs, stream, riders=None):
+def bwd_ex(lib, x, w, dy, dx, E, dw, scratch, slabs, stream, riders=None, frag=None):
     """sgmcmc_conv3x3_bwd_ex, or sgmcmc_conv3x3_bwd_ride when ``riders`` (take_riders) come along; dw None / slabs (a
-    ctypes.c_int) not None: the launch's own slabs are left for a later reduction -> the error code"""
+    ctypes.c_int) not None: the launch's own slabs are left for a later reduction; ``frag``: w's data-gradient fragments
+    (``frags``) -- the same launch with that role reading them (sgmcmc_conv3x3_wfrag_bwd) -> the error code"""
     n, c, hw = x.shape[0], x.shape[1], x.shape[2]
-    args = (x.data_ptr(), w.data_ptr(), dy.data_ptr(), dx.data_ptr(), ctypes.byref(E), 0 if dw is None else dw.data_ptr(),
-            scratch.data_ptr(), n, c, hw, None if slabs is None else ctypes.byref(slabs))
-    if not riders:
+    args = (x.data_ptr(), (w if frag is None else frag).data_ptr(), dy.data_ptr(), dx.data_ptr(), ctypes.byref(E),
+            0 if dw is None else dw.data_ptr(), scratch.data_ptr(), n, c, hw, None if slabs is None else ctypes.byref(slabs))
+    if not riders and frag is None:
         return lib.sgmcmc_conv3x3_bwd_ex(*args, stream)
-    jobs = _fill_jobs((_hip.ReduceJob * len(riders))(), riders)
-    return lib.sgmcmc_conv3x3_bwd_ride(*args, ctypes.cast(jobs, ctypes.c_void_p), len(riders), int(RIDERS_FIRST), stream)
+    n_jobs = len(riders) if riders else 0
+    jobs = ctypes.cast(_fill_jobs((_hip.ReduceJob * n_jobs)(), riders), ctypes.c_void_p) if n_jobs else None
+    if frag is None:
+        return lib.sgmcmc_conv3x3_bwd_ride(*args, jobs, n_jobs, int(RIDERS_FIRST), stream)
+    return lib.sgmcmc_conv3x3_wfrag_bwd(*args, jobs, n_jobs, int(RIDERS_FIRST), WEIGHT_FRAG_FORM[(c, hw, "dgrad")], stream)
 
 
 # ---- weight gradients off the critical path (MEASURED SLOWER: off by default) ------------------------------------
@@ -718,8 +789,17 @@ class _ConvStem(torch.autograd.Function):
         n = x.shape[0]
         y = torch.empty((n, 16, 32, 32), dtype=torch.float32, device=x.device)
         stats = torch.empty((16, 4 * n, 2), dtype=torch.float64, device=x.device) if want_stats else None
-        err = lib.sgmcmc_conv_stem_fwd(x.data_ptr(), w.data_ptr(), y.data_ptr(),
-                                       0 if stats is None else stats.data_ptr(), n, _stream())
+        # (the first launch of a gradient evaluation: the scope's queued fragment jobs trail its grid -- WEIGHT_FRAGS)
+        carried = take_frag_jobs(x.device) if _frag_queue else []
+        if carried:
+            err = lib.sgmcmc_conv_stem_fwd_frags(x.data_ptr(), w.data_ptr(), y.data_ptr(),
+                                                 0 if stats is None else stats.data_ptr(), n,
+                                                 ctypes.cast(_frag_jobs(carried), ctypes.c_void_p), len(carried),
+                                                 int(FRAG_JOBS_FIRST), _stream())
+            _frag_valid.update(id(q) for q in carried)
+        else:
+            err = lib.sgmcmc_conv_stem_fwd(x.data_ptr(), w.data_ptr(), y.data_ptr(),
+                                           0 if stats is None else stats.data_ptr(), n, _stream())
         if err:
             _hip.check(err, "sgmcmc_conv_stem_fwd")
         ctx.save_for_backward(x, w)

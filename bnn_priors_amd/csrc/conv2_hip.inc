@@ -91,6 +91,45 @@ __global__ __launch_bounds__(256) void weight_frag_kernel(FragJobs J) {
   if (q.dgrad) q.dgrad[e] = q.w[((size_t)ch * C + n) * 9 + (8 - rs)];
 }
 
+// The same fragments four at a time, for workgroups that TRAIL another kernel's grid (convstem::fwd_frags_kernel: the
+// preparation costs no launch): block `blk` of job q writes float4 blk * 256 + tid of each buffer -- the four k-steps of
+// one (tile, half, q4, lane) -- so a job is ceil(9 C^2 / 1024) blocks, 243 for googleresnet's 16 convolutions.
+__host__ __device__ __forceinline__ int frag_blocks4(int channels) { return (9 * channels * channels / 4 + 255) / 256; }
+__device__ __forceinline__ void frag_block4(const FragJob& q, int blk) {
+  const int C = q.channels, KS = q.ks, KK = C / 4 / KS, QW = 9 * KK;
+  const int v = blk * 256 + (int)threadIdx.x;                                        // output float4 index
+  if (4 * v >= 9 * C * C) return;
+  const int lane = v & 63, rest = v >> 6;
+  const int q4 = rest % (QW / 4), h = (rest / (QW / 4)) % KS, ct = rest / (QW / 4) / KS;
+  const int n = ct * 16 + (lane & 15);
+  float f[4], d[4];
+#pragma unroll
+  for (int comp = 0; comp < 4; ++comp) {
+    const int qi = 4 * q4 + comp, rs = qi / KK, k2 = qi % KK;
+    const int ch = 4 * (h * KK + k2) + (lane >> 4);
+    f[comp] = q.fwd ? q.w[((size_t)n * C + ch) * 9 + rs] : 0.f;
+    d[comp] = q.dgrad ? q.w[((size_t)ch * C + n) * 9 + (8 - rs)] : 0.f;
+  }
+  if (q.fwd) reinterpret_cast<float4*>(q.fwd)[v] = make_float4(f[0], f[1], f[2], f[3]);
+  if (q.dgrad) reinterpret_cast<float4*>(q.dgrad)[v] = make_float4(d[0], d[1], d[2], d[3]);
+}
+// sgmcmc_frag_job[n] (n <= SGMCMC_FRAG_JOBS) -> FragJobs with `blocks_of(channels)` blocks per job; -> 0 or the refusal
+template <typename BlocksOf>
+inline int frag_jobs_from_abi(const sgmcmc_frag_job* jobs, int n, BlocksOf blocks_of, FragJobs& J) {
+  J.n = n;
+  int blocks = 0;
+  for (int j = 0; j < n; ++j) {
+    const sgmcmc_frag_job& q = jobs[j];
+    const int c = q.channels;
+    if (!q.w || (!q.fwd && !q.dgrad) || !(c == 16 || c == 32 || c == 64)) return (int)hipErrorInvalidValue;
+    J.job[j] = {q.w, q.fwd, q.dgrad, c, c == 64 ? 2 : 1};      // K split of the 8x8 stage (Cfg::KS)
+    J.first_block[j] = blocks;
+    blocks += blocks_of(c);
+  }
+  J.first_block[n] = blocks;
+  return 0;
+}
+
 // ---------------------------------------------------------------- epilogue reductions without a barrier of their own
 // A wave leaves ITS per-channel partials in LDS right after its MFMAs (channel n lives in lanes n, n+16, n+32, n+48:
 // fixed xor tree); the four waves' partials are combined -- in wave order, in double -- by threads 0..15 AFTER the
@@ -647,18 +686,10 @@ extern "C" int sgmcmc_conv3x3_prepare_weights(const sgmcmc_frag_job* jobs, int n
   hipStream_t s = (hipStream_t)stream;
   for (int base = 0; base < n_jobs; base += SGMCMC_FRAG_JOBS) {
     conv2::FragJobs J;
-    J.n = n_jobs - base < SGMCMC_FRAG_JOBS ? n_jobs - base : SGMCMC_FRAG_JOBS;
-    int blocks = 0;
-    for (int j = 0; j < J.n; ++j) {
-      const sgmcmc_frag_job& q = jobs[base + j];
-      const int c = q.channels;
-      if (!q.w || (!q.fwd && !q.dgrad) || !(c == 16 || c == 32 || c == 64)) return (int)hipErrorInvalidValue;
-      J.job[j] = {q.w, q.fwd, q.dgrad, c, c == 64 ? 2 : 1};      // K split of the 8x8 stage (Cfg::KS)
-      J.first_block[j] = blocks;
-      blocks += (9 * c * c + 255) / 256;
-    }
-    J.first_block[J.n] = blocks;
-    SGMCMC_LAUNCH(conv2::weight_frag_kernel, dim3((unsigned)blocks), dim3(256), 0, s, J);
+    const int n = n_jobs - base < SGMCMC_FRAG_JOBS ? n_jobs - base : SGMCMC_FRAG_JOBS;
+    if (const int bad = conv2::frag_jobs_from_abi(jobs + base, n, [](int c) { return (9 * c * c + 255) / 256; }, J))
+      return bad;
+    SGMCMC_LAUNCH(conv2::weight_frag_kernel, dim3((unsigned)J.first_block[n]), dim3(256), 0, s, J);
   }
   return (int)hipGetLastError();
 }

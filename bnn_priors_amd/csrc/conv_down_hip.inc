@@ -597,14 +597,14 @@ __device__ __forceinline__ int tap_offset(int kidx) {  // LDS offset of tap kidx
   return ci * CS + r * WP + s;
 }
 
+// (block `b` of the stem's own `n_blocks` = 4 per image)
 template <bool STATS>
-__global__ __launch_bounds__(256) void fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                  float* __restrict__ y, double* __restrict__ stats,
-                                                  int n_slices) {
+__device__ __forceinline__ void fwd_block(int b, int n_blocks, const float* __restrict__ x, const float* __restrict__ w,
+                                          float* __restrict__ y, double* __restrict__ stats, int n_slices) {
   __shared__ float in_s[CIN * CS];
   __shared__ float red[128];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int bid = conv::xcd_remap<16>((int)blockIdx.x, (int)gridDim.x);
+  const int bid = conv::xcd_remap<16>(b, n_blocks);
   const int band = bid % BANDS, img = bid / BANDS;
   const int y0 = band * ROWS;
   stage(in_s, x + (size_t)img * CIN * HW * HW, y0, tid);
@@ -635,6 +635,35 @@ __global__ __launch_bounds__(256) void fwd_kernel(const float* __restrict__ x, c
   }
   if (STATS)
     conv::band_stats<4>(vals, s1, ROWS * HW, red, stats + (size_t)(img * BANDS + band) * 2, (size_t)n_slices * 2);
+}
+
+template <bool STATS>
+__global__ __launch_bounds__(256) void fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                  float* __restrict__ y, double* __restrict__ stats,
+                                                  int n_slices) {
+  fwd_block<STATS>((int)blockIdx.x, (int)gridDim.x, x, w, y, stats, n_slices);
+}
+
+// The stem as the CARRIER of the trunk's weight fragments: it is the first launch of a gradient evaluation and reads no
+// trunk weight, so behind its own n_own workgroups trail the blocks of up to SGMCMC_FRAG_JOBS fragment jobs
+// (conv2::frag_block4: the buffers sgmcmc_conv3x3_prepare_weights would write, without its launch) -- the structure of
+// conv3x3_bwd_kernel's riders.  The first consumer is a later launch: the kernel boundary is the synchronisation.
+template <bool STATS>
+__global__ __launch_bounds__(256) void fwd_frags_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                        float* __restrict__ y, double* __restrict__ stats,
+                                                        int n_slices, int n_own, int jobs_first, conv2::FragJobs J) {
+  // (jobs_first: the fragment blocks lead the grid, padded to a multiple of 8 so that the stem's blocks keep their XCDs)
+  const int n_lead = jobs_first ? (J.first_block[J.n] + 7) & ~7 : 0;
+  const int b = (int)blockIdx.x - n_lead;
+  if (b >= 0 && b < n_own) {
+    fwd_block<STATS>(b, n_own, x, w, y, stats, n_slices);
+    return;
+  }
+  const int r = jobs_first ? (int)blockIdx.x : b - n_own;
+  if (r >= J.first_block[J.n]) return;      // padding
+  int j = 0;
+  while (j + 1 < J.n && r >= J.first_block[j + 1]) ++j;
+  conv2::frag_block4(J.job[j], r - J.first_block[j]);
 }
 
 // dw[co][kidx] slabs: wave = pixel quarter of the band; per 4-pixel k-step one A fetch (dy) and two B
@@ -699,6 +728,23 @@ extern "C" int sgmcmc_conv_stem_fwd(const float* x, const float* w, float* y, do
   hipStream_t s = (hipStream_t)stream;
   if (stats) SGMCMC_LAUNCH(convstem::fwd_kernel<true>, grid, block, 0, s, x, w, y, stats, n_img * convstem::BANDS);
   else SGMCMC_LAUNCH(convstem::fwd_kernel<false>, grid, block, 0, s, x, w, y, nullptr, 0);
+  return (int)hipGetLastError();
+}
+
+// ... with the fragments of up to SGMCMC_FRAG_JOBS trunk convolutions prepared by trailing workgroups of the launch
+extern "C" int sgmcmc_conv_stem_fwd_frags(const float* x, const float* w, float* y, double* stats, int n_img,
+                                          const sgmcmc_frag_job* jobs, int n_jobs, int jobs_first, void* stream) {
+  if (n_jobs == 0) return sgmcmc_conv_stem_fwd(x, w, y, stats, n_img, stream);
+  SGMCMC_FRESH_ERROR_STATE();
+  if (!x || !w || !y || n_img <= 0 || !jobs || n_jobs < 0 || n_jobs > SGMCMC_FRAG_JOBS) return (int)hipErrorInvalidValue;
+  conv2::FragJobs J;
+  if (const int bad = conv2::frag_jobs_from_abi(jobs, n_jobs, conv2::frag_blocks4, J)) return bad;
+  const int n_own = n_img * convstem::BANDS;
+  const int first = jobs_first != 0, n_frag = first ? (J.first_block[n_jobs] + 7) & ~7 : J.first_block[n_jobs];
+  const dim3 grid((unsigned)(n_own + n_frag)), block(256);
+  hipStream_t s = (hipStream_t)stream;
+  if (stats) SGMCMC_LAUNCH(convstem::fwd_frags_kernel<true>, grid, block, 0, s, x, w, y, stats, n_own, n_own, first, J);
+  else SGMCMC_LAUNCH(convstem::fwd_frags_kernel<false>, grid, block, 0, s, x, w, y, nullptr, 0, n_own, first, J);
   return (int)hipGetLastError();
 }
 

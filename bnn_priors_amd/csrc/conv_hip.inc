@@ -354,8 +354,17 @@ struct Cfg {
 // shortcut carries back to the block's input (replaces an ATen add and the dz tensor it would read).
 // SUMS: the epilogue also leaves the partial sums the NEXT BatchNorm backward needs (band_sums above), from the
 // registers -- the separate sums launch of that BatchNorm (5 us, 21 per step) disappears.
+// FRAG != 0: `w` is not the raw [co][ci][3][3] tensor but its PREPARED FRAGMENTS (conv2::weight_frag_kernel's layout:
+// forward order, or transposed + flipped with TRANSPOSE_W -- the permutation was done once per gradient evaluation, not
+// by each of the launch's 512 workgroups).  Tile ct is 9C/16 float4 per lane, float4 f of lane l at
+// w[((ct * 9C/16 + f) * 64 + l) * 4]; with KS = 2 at 64 channels, else 1, KK = C / 4 / KS, f = h * (9 KK / 4) + q4:
+// component j is breg[rs][h * KK + k2], (rs, k2) = ((4 q4 + j) / KK, (4 q4 + j) % KK) -- the SAME register values as
+// the raw route's fill, so the same bits.  FRAG_LDS: the tile is copied to LDS linearly (16-byte loads and stores) and
+// every lane fills its registers with 9C/16 ds_read_b128; FRAG_REG: 9C/16 16-byte global loads straight into the
+// registers, the slab's LDS stays unused.
+constexpr int FRAG_LDS = 1, FRAG_REG = 2;
 template <int C, int HW, int ROWS, bool TRANSPOSE_W, bool STATS, bool EPI = false, bool SUMS = false, bool BNIN = false,
-          bool AFF = false>
+          bool AFF = false, int FRAG = 0>
 __device__ __forceinline__ void conv3x3_body(int b, const float* __restrict__ x, const float* __restrict__ w,
                                              float* __restrict__ y, double* __restrict__ stats,
                                              int n_slices, const BwdEpilogue* E = nullptr,
@@ -373,6 +382,9 @@ __device__ __forceinline__ void conv3x3_body(int b, const float* __restrict__ x,
   const int y0 = band * ROWS;
   SGMCMC_STAMP(0);
   SGMCMC_STAMP(7);
+  static_assert(!FRAG || !BNIN, "the fragment route does not fold a BatchNorm into its staging");
+  constexpr int NF = 9 * C / 16;                      // FRAG: float4 per lane of a tile's fragments
+  float4 fr[FRAG == FRAG_REG ? NF : 1];
 
   // ---- operands: the 16 x K weight slab (K ordered (ci, r, s) as in memory) and the input band with its halo,
   // every global load of both in flight before the first LDS store
@@ -438,6 +450,17 @@ __device__ __forceinline__ void conv3x3_body(int b, const float* __restrict__ x,
         w_s[slab_at(4 * i + 2)] = q.z; w_s[slab_at(4 * i + 3)] = q.w;
       });
       stage_store<C * ROWSH * V / 2, float4>(ri, st_in);
+    } else if (FRAG == FRAG_LDS) {
+      const float4* __restrict__ src = reinterpret_cast<const float4*>(w + (size_t)ct * 16 * G::K);  // the tile's fragments
+      stage2<4 * G::K, float4, C * ROWSH * V / 2, float4>(
+          [&](int i) { return src[i]; },
+          [&](int i, const float4& q) { *reinterpret_cast<float4*>(w_s + 4 * i) = q; },
+          ld_in, st_in);
+    } else if (FRAG == FRAG_REG) {
+      const float4* __restrict__ src = reinterpret_cast<const float4*>(w + (size_t)ct * 16 * G::K) + lane;
+#pragma unroll
+      for (int f = 0; f < NF; ++f) fr[f] = src[f * 64];
+      stage<C * ROWSH * V / 2, float4>(ld_in, st_in);
     } else if (!TRANSPOSE_W) {
       const float4* __restrict__ src = reinterpret_cast<const float4*>(w + (size_t)ct * 16 * G::K);  // contiguous
       stage2<4 * G::K, float4, C * ROWSH * V / 2, float4>(
@@ -485,10 +508,24 @@ __device__ __forceinline__ void conv3x3_body(int b, const float* __restrict__ x,
   // ---- this wave's B operands: lane (n = lane & 15, k = lane >> 4) holds w_s[n][4*kk + k][rs]
   const int n = lane & 15, kq = lane >> 4;
   float breg[9][C / 4];
+  if (FRAG) {
+    constexpr int KS = C == 64 ? 2 : 1, KK = C / 4 / KS, QW4 = 9 * KK / 4;
 #pragma unroll
-  for (int rs = 0; rs < 9; ++rs)
+    for (int f = 0; f < NF; ++f) {
+      const float4 q = FRAG == FRAG_REG ? fr[f] : *reinterpret_cast<const float4*>(w_s + (f * 64 + lane) * 4);
+      const float qv[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
-    for (int kk = 0; kk < C / 4; ++kk) breg[rs][kk] = w_s[n * G::KP + (4 * kk + kq) * 9 + rs];
+      for (int j = 0; j < 4; ++j) {
+        const int qi = 4 * (f % QW4) + j;
+        breg[qi / KK][(f / QW4) * KK + qi % KK] = qv[j];
+      }
+    }
+  } else {
+#pragma unroll
+    for (int rs = 0; rs < 9; ++rs)
+#pragma unroll
+      for (int kk = 0; kk < C / 4; ++kk) breg[rs][kk] = w_s[n * G::KP + (4 * kk + kq) * 9 + rs];
+  }
 
   // ---- pixel tiles
   constexpr int NACC = G::PT_W == 1 ? 2 : G::PT_W;  // a single tile splits its K chain in two
@@ -633,12 +670,38 @@ __device__ __forceinline__ void conv3x3_body(int b, const float* __restrict__ x,
   SGMCMC_STAMP(6);
 }
 
-template <int C, int HW, int ROWS, bool TRANSPOSE_W, bool STATS>
+template <int C, int HW, int ROWS, bool TRANSPOSE_W, bool STATS, int FRAG = 0>
 __global__ __launch_bounds__(256) void conv3x3_kernel(const float* __restrict__ x,
                                                       const float* __restrict__ w,
                                                       float* __restrict__ y, double* __restrict__ stats,
                                                       int n_slices) {
-  conv3x3_body<C, HW, ROWS, TRANSPOSE_W, STATS>(xcd_remap<C>((int)blockIdx.x, (int)gridDim.x), x, w, y, stats, n_slices);
+  conv3x3_body<C, HW, ROWS, TRANSPOSE_W, STATS, false, false, false, false, FRAG>(
+      xcd_remap<C>((int)blockIdx.x, (int)gridDim.x), x, w, y, stats, n_slices);
+}
+
+// the forward with its statistics on prepared fragments (`frag`: the convolution's forward fragments); FRAG_REG leaves
+// the slab's share of the LDS unrequested
+template <int C, int HW, int ROWS>
+int launch_conv3x3_wfrag(const float* x, const float* frag, float* y, int n_img, double* stats, int form, hipStream_t s) {
+  using G = Cfg<C, HW, ROWS>;
+  const dim3 grid((unsigned)(n_img * G::BANDS * G::CT)), block(256);
+  auto kl = conv3x3_kernel<C, HW, ROWS, false, true, FRAG_LDS>;
+  auto kr = conv3x3_kernel<C, HW, ROWS, false, true, FRAG_REG>;
+  constexpr size_t LDS_REG = G::LDS_BYTES - (size_t)16 * G::KP * sizeof(float);
+  static_assert(LDS_REG >= 128 * sizeof(float), "band_stats reduces in the launch's LDS");
+  static bool attr_done = false;
+  if (!attr_done) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kl), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)G::LDS_BYTES);
+    if (e == hipSuccess)
+      e = hipFuncSetAttribute(reinterpret_cast<const void*>(kr), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_REG);
+    if (e != hipSuccess) return (int)e;
+    attr_done = true;
+  }
+  const int n_slices = n_img * G::BANDS;
+  if (form == FRAG_REG) SGMCMC_LAUNCH(kr, grid, block, LDS_REG, s, x, frag, y, stats, n_slices);
+  else SGMCMC_LAUNCH(kl, grid, block, G::LDS_BYTES, s, x, frag, y, stats, n_slices);
+  return (int)hipGetLastError();
 }
 
 template <int C, int HW, int ROWS>
@@ -1042,7 +1105,8 @@ __host__ __device__ __forceinline__ int ride_blocks(const RideJobs& R) {
 // (3 waves per SIMD = 3 workgroups per CU, what the LDS footprint admits: the ADD + SUMS variant at 16 channels sat two
 // registers above that step.  At 64 channels the data gradient's 80 KB of LDS admit two workgroups per CU whatever is
 // requested: asking for three only capped the registers at 168 and made the ADD + SUMS instantiation spill: two there)
-template <int C, int HW, int ROWS, bool EPI, bool SUMS, bool MULT = false>
+// FRAG: the data-gradient role reads `w` as the convolution's prepared DATA-GRADIENT fragments (conv3x3_body, FRAG)
+template <int C, int HW, int ROWS, bool EPI, bool SUMS, bool MULT = false, int FRAG = 0>
 __global__ __launch_bounds__(256, (MULT || C >= 64) ? 2 : 3) void conv3x3_bwd_kernel(const float* __restrict__ x,
                                                           const float* __restrict__ w,
                                                           const float* __restrict__ dy,
@@ -1068,7 +1132,8 @@ __global__ __launch_bounds__(256, (MULT || C >= 64) ? 2 : 3) void conv3x3_bwd_ke
   if (b < n_wrw) {
     conv3x3_wrw_body<C, HW, ROWS, MULT>(xcd_remap<C>(b, n_wrw), x, dy, part, n_items, E.wrw_mult);
   }
-  else conv3x3_body<C, HW, ROWS, true, false, EPI, SUMS>(xcd_remap<C>(b - n_wrw, n_dgrad), dy, w, dx, nullptr, 0, &E);
+  else conv3x3_body<C, HW, ROWS, true, false, EPI, SUMS, false, false, FRAG>(xcd_remap<C>(b - n_wrw, n_dgrad), dy, w, dx,
+                                                                             nullptr, 0, &E);
 }
 
 // ---- host-side pieces every convolution entry point shares -----------------------------------------------------
@@ -1194,6 +1259,40 @@ int launch_bwd(const float* x, const float* w, const float* dy, float* dx, float
   return finish_slabs(n_slabs, P, s, {{part, C * C * 9, dw, 9}});
 }
 
+// launch_bwd's merged launch with the data-gradient role on prepared fragments, for what the leapfrog step runs: the
+// sums epilogue (with or without the shortcut's add), one minibatch, with or without riders; the slabs are always left
+// to the caller (*n_slabs) or reduced here, as launch_bwd does
+template <int C, int HW, int ROWS>
+int launch_bwd_wfrag(const float* x, const float* frag, const float* dy, float* dx, float* dw, float* part, int n_img,
+                     int* n_slabs, hipStream_t s, const BwdEpilogue& E, const RideJobs& R, int form) {
+  using G = WrwCfg<C, HW, ROWS>;
+  using F = Cfg<C, HW, ROWS>;
+  const int n_items = n_img * G::BANDS, P = (n_items + G::ITEMS - 1) / G::ITEMS;
+  const int n_dgrad = n_img * F::BANDS * F::CT, n_wrw = P * G::CT;
+  const size_t lds = F::LDS_BYTES > G::LDS_BYTES ? F::LDS_BYTES : G::LDS_BYTES;
+  auto l01 = conv3x3_bwd_kernel<C, HW, ROWS, false, true, false, FRAG_LDS>;
+  auto l11 = conv3x3_bwd_kernel<C, HW, ROWS, true, true, false, FRAG_LDS>;
+  auto r01 = conv3x3_bwd_kernel<C, HW, ROWS, false, true, false, FRAG_REG>;
+  auto r11 = conv3x3_bwd_kernel<C, HW, ROWS, true, true, false, FRAG_REG>;
+  static bool attr_done = false;
+  if (!attr_done) {
+    for (const void* f : {reinterpret_cast<const void*>(l01), reinterpret_cast<const void*>(l11),
+                          reinterpret_cast<const void*>(r01), reinterpret_cast<const void*>(r11)}) {
+      const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) return (int)e;
+    }
+    attr_done = true;
+  }
+  BwdEpilogue Ev = E;
+  Ev.n_slices = n_img * F::BANDS;
+  Ev.wrw_mult = 1;
+  const dim3 grid((unsigned)(n_dgrad + n_wrw + ride_blocks(R)));
+  const bool epi = E.e_dout != nullptr, reg = form == FRAG_REG;
+  auto k = epi ? (reg ? r11 : l11) : (reg ? r01 : l01);
+  SGMCMC_LAUNCH(k, grid, dim3(256), lds, s, x, frag, dy, dx, part, n_dgrad, n_items, Ev, R);
+  return finish_slabs(n_slabs, P, s, {{part, C * C * 9, dw, 9}});
+}
+
 }  // namespace conv
 
 // data gradient AND weight gradient of the convolution in one launch (+ the slab reduction)
@@ -1241,14 +1340,10 @@ extern "C" int sgmcmc_conv3x3_bwd_ex(const float* x, const float* w, const float
   return conv3x3_bwd_ex_with(x, w, dy, dx, epi, dw, scratch, n_img, channels, hw, deferred_slabs, stream, conv::RideJobs{});
 }
 
-// ... with up to SGMCMC_RIDE_JOBS slab reductions of earlier launches riding in the grid (conv::RideJobs)
-extern "C" int sgmcmc_conv3x3_bwd_ride(const float* x, const float* w, const float* dy, float* dx,
-                                       const sgmcmc_conv_bwd_epilogue* epi, float* dw, float* scratch, int n_img,
-                                       int channels, int hw, int* deferred_slabs, const sgmcmc_reduce_job* jobs,
-                                       int n_jobs, int riders_first, void* stream) {
-  SGMCMC_FRESH_ERROR_STATE();
+// sgmcmc_reduce_job[n_jobs] -> conv::RideJobs, with the checks of every entry point that takes riders
+static int riders_from_abi(const sgmcmc_reduce_job* jobs, int n_jobs, int riders_first, conv::RideJobs& R) {
   if (n_jobs < 0 || n_jobs > SGMCMC_RIDE_JOBS || (n_jobs && !jobs)) return (int)hipErrorInvalidValue;
-  conv::RideJobs R{};
+  R = conv::RideJobs{};
   R.n = n_jobs;
   R.first = riders_first != 0;
   int blocks = 0;
@@ -1260,7 +1355,53 @@ extern "C" int sgmcmc_conv3x3_bwd_ride(const float* x, const float* w, const flo
     blocks += conv::reduce_blocks(q.n_slabs, q.numel);
   }
   R.first_block[n_jobs] = blocks;
+  return 0;
+}
+
+// ... with up to SGMCMC_RIDE_JOBS slab reductions of earlier launches riding in the grid (conv::RideJobs)
+extern "C" int sgmcmc_conv3x3_bwd_ride(const float* x, const float* w, const float* dy, float* dx,
+                                       const sgmcmc_conv_bwd_epilogue* epi, float* dw, float* scratch, int n_img,
+                                       int channels, int hw, int* deferred_slabs, const sgmcmc_reduce_job* jobs,
+                                       int n_jobs, int riders_first, void* stream) {
+  SGMCMC_FRESH_ERROR_STATE();
+  conv::RideJobs R{};
+  if (const int bad = riders_from_abi(jobs, n_jobs, riders_first, R)) return bad;
   return conv3x3_bwd_ex_with(x, w, dy, dx, epi, dw, scratch, n_img, channels, hw, deferred_slabs, stream, R);
+}
+
+// ---- the same forward and merged backward launches on PREPARED weight fragments (conv3x3_body, FRAG) ------------------
+static int wfrag_form(int form) { return form == 1 ? conv::FRAG_LDS : form == 2 ? conv::FRAG_REG : 0; }
+
+extern "C" int sgmcmc_conv3x3_wfrag_fwd(const float* x, const float* frag_fwd, float* y, int n_img, int channels, int hw,
+                                        double* stats, int form, void* stream) {
+  SGMCMC_FRESH_ERROR_STATE();
+  const int f = wfrag_form(form);
+  if (!x || !frag_fwd || !y || !stats || n_img <= 0 || !f) return (int)hipErrorInvalidValue;
+  hipStream_t s = (hipStream_t)stream;
+  SGMCMC_FOR_TRUNK_SHAPE(channels, hw, conv::launch_conv3x3_wfrag<C, HW, ROWS>(x, frag_fwd, y, n_img, stats, f, s));
+}
+
+static int conv3x3_wfrag_bwd_with(const float* x, const float* frag, const float* dy, float* dx, float* dw, float* scratch,
+                                  int n_img, int channels, int hw, int* d, hipStream_t s, const conv::BwdEpilogue& E,
+                                  const conv::RideJobs& R, int form) {
+  SGMCMC_FOR_TRUNK_SHAPE(channels, hw, conv::launch_bwd_wfrag<C, HW, ROWS>(x, frag, dy, dx, dw, scratch, n_img, d, s, E, R, form));
+}
+
+extern "C" int sgmcmc_conv3x3_wfrag_bwd(const float* x, const float* frag_dgrad, const float* dy, float* dx,
+                                        const sgmcmc_conv_bwd_epilogue* epi, float* dw, float* scratch, int n_img,
+                                        int channels, int hw, int* deferred_slabs, const sgmcmc_reduce_job* jobs,
+                                        int n_jobs, int riders_first, int form, void* stream) {
+  SGMCMC_FRESH_ERROR_STATE();
+  const int f = wfrag_form(form);
+  if (!x || !frag_dgrad || !dy || !dx || !epi || !scratch || n_img <= 0 || (!dw && !deferred_slabs) || !f)
+    return (int)hipErrorInvalidValue;
+  conv::BwdEpilogue E;
+  if (const int bad = conv::epilogue_from_abi(epi, n_img, E)) return bad;
+  if (!E.s_partial || E.wrw_mult > 1) return (int)hipErrorInvalidValue;      // the step's variants only (sgmcmc_hip.h)
+  conv::RideJobs R{};
+  if (const int bad = riders_from_abi(jobs, n_jobs, riders_first, R)) return bad;
+  return conv3x3_wfrag_bwd_with(x, frag_dgrad, dy, dx, dw, scratch, n_img, channels, hw, deferred_slabs, (hipStream_t)stream,
+                                E, R, f);
 }
 
 #ifdef SGMCMC_STAMPS

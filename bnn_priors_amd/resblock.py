@@ -88,7 +88,7 @@ def _conv_bn_fwd(lib, x, w, g, b, rm, rv, mom, eps, residual, s, G=1):
     else:
         slices = lib.sgmcmc_conv3x3_stat_slices(n, c, hw)
         stats = torch.empty((c, slices, 2), dtype=torch.float64, device=x.device)
-        err = lib.sgmcmc_conv3x3(x.data_ptr(), w.data_ptr(), y.data_ptr(), n, c, hw, 0, stats.data_ptr(), s)
+        err = _conv.forward_stats(lib, x, w, y, stats, s)
     if err:
         _hip.check(err, "sgmcmc_conv3x3")
     err = _bn.train_fwd(lib, y, residual, g, b, rm, rv, mom, eps, 1, n, c, hw * hw, out, saved, None, stats, slices, s, G)

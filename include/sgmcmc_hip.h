@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGMCMC_ABI_VERSION 21
+#define SGMCMC_ABI_VERSION 22
 #define SGMCMC_CHUNK 4096 /* default elements per arena chunk = 256 threads x 4 items x 4 elements */
 #define SGMCMC_CHUNK_SMALL 1024 /* small models: one item per thread, 4x more workgroups */
 #define SGMCMC_NSUMS 6
@@ -555,6 +555,21 @@ int sgmcmc_conv3x3_frag_fwd(const float* x, const float* frag_fwd, float* y, int
 int sgmcmc_conv3x3_frag_bwd(const float* x, const float* frag_dgrad, const float* dy, float* dx,
                             const sgmcmc_conv_bwd_epilogue* epi, float* dw, float* scratch, int n_img, int channels,
                             int hw, int* deferred_slabs, void* stream);
+/* ---- sgmcmc_conv3x3 / sgmcmc_conv3x3_bwd_ride themselves on those fragments (csrc/conv_hip.inc, FRAG) ----
+ * The default kernels of the 128-image step -- same tiling, same statistics slices, same slabs, same MFMA order, hence
+ * the SAME BITS as the raw-weight entry points -- whose workgroups read their B operands from the fragments of
+ * sgmcmc_conv3x3_prepare_weights (or of sgmcmc_conv_stem_fwd_frags, which prepares them without a launch) instead of
+ * each permuting the raw [co][ci][3][3] tensor.  form: 1 = the tile's fragments are copied to LDS linearly and read back
+ * 16 bytes per lane; 2 = 16-byte global loads straight into the operand registers, no weight slab in LDS.
+ * sgmcmc_conv3x3_wfrag_fwd: sgmcmc_conv3x3 with transpose_w = 0 and stats (required), on frag_fwd.
+ * sgmcmc_conv3x3_wfrag_bwd: sgmcmc_conv3x3_bwd_ride (n_jobs = 0: sgmcmc_conv3x3_bwd_ex) on frag_dgrad, for the
+ * epilogues of the leapfrog step only: s_partial is required (with or without e_dout), wrw_mult must be 0 or 1. */
+int sgmcmc_conv3x3_wfrag_fwd(const float* x, const float* frag_fwd, float* y, int n_img, int channels, int hw,
+                             double* stats, int form, void* stream);
+int sgmcmc_conv3x3_wfrag_bwd(const float* x, const float* frag_dgrad, const float* dy, float* dx,
+                             const sgmcmc_conv_bwd_epilogue* epi, float* dw, float* scratch, int n_img, int channels,
+                             int hw, int* deferred_slabs, const sgmcmc_reduce_job* jobs, int n_jobs, int riders_first,
+                             int form, void* stream);
 
 
 /* The two convolutions that open a down-sampling ResNet block, as one operator (they read the same input;
@@ -588,6 +603,13 @@ int sgmcmc_conv_down_bwd_ex(const float* x, const float* w_main, const float* w_
  * forward (+ optional per-band statistics [16][4 n_img][2]) and weight gradient (the images take no
  * gradient); scratch / deferred_slabs as for sgmcmc_conv3x3_bwd. */
 int sgmcmc_conv_stem_fwd(const float* x, const float* w, float* y, double* stats, int n_img, void* stream);
+/* ... as the carrier of the trunk's weight fragments: the stem is the first launch of a gradient evaluation and reads no
+ * trunk weight, so n_jobs <= SGMCMC_FRAG_JOBS jobs of sgmcmc_conv3x3_prepare_weights (the same buffers, the same
+ * values) are done by workgroups that trail its grid -- no launch of their own.  Consumers must be enqueued later on
+ * `stream`.  n_jobs = 0 is sgmcmc_conv_stem_fwd.  jobs_first != 0: those workgroups lead the grid (padded to 8 blocks)
+ * instead of trailing it. */
+int sgmcmc_conv_stem_fwd_frags(const float* x, const float* w, float* y, double* stats, int n_img,
+                               const sgmcmc_frag_job* jobs, int n_jobs, int jobs_first, void* stream);
 int64_t sgmcmc_conv_stem_scratch_floats(int n_img);
 int sgmcmc_conv_stem_wrw(const float* x, const float* dy, float* dw, float* scratch, int n_img,
                          int* deferred_slabs, void* stream);

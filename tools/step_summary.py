@@ -65,10 +65,13 @@ def conv_shape(name):
 def row_name(rows_of_step, i):
     "bench.py's roofline row for dispatch i of a step, or None"
     name = rows_of_step[i]["Kernel_Name"]
-    m = re.search(r"conv::conv3x3_kernel<(\d+), (\d+), (\d+), false, true>", name)
+    # (a trailing integer: where the workgroups take their B operands from -- 0 the raw weights, 1 / 2 prepared fragments
+    # through LDS / straight into registers, conv.WEIGHT_FRAGS; the same launch role, hence the same row)
+    m = re.search(r"conv::conv3x3_kernel<(\d+), (\d+), (\d+), false, true(?:, \d+)?>", name)
     if m:
         return "conv::conv3x3_kernel<%s,%s,%s,stats>" % m.groups()
-    m = re.search(r"conv::conv3x3_bwd_kernel<(\d+), (\d+), (\d+), (true|false), (true|false)(?:, (?:true|false))?>", name)
+    m = re.search(r"conv::conv3x3_bwd_kernel<(\d+), (\d+), (\d+), (true|false), (true|false)(?:, (?:true|false))?(?:, \d+)?>",
+                  name)
     if m:       # (a third flag since round 4: the many-minibatch instantiation; the step runs `false`)
         c, hw, r, epi, sums = m.groups()
         tag = ",".join(t for t, on in (("ADD", epi), ("SUMS", sums)) if on == "true")
