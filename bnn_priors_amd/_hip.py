@@ -24,7 +24,7 @@ INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 SOURCES = [os.path.join(_HERE, "csrc", "sgmcmc_hip.hip")]
 SOURCE = SOURCES[0]
 
-ABI_VERSION = 22
+ABI_VERSION = 23
 CHUNK = 4096
 CHUNK_SMALL = 1024
 NSUMS = 6
@@ -189,6 +189,12 @@ FIT_TILE_DOUBLES, FIT_TILE_ROWS, FIT_MAX_BLOCKS, FIT_PART, FIT_STATE = 5120, 512
 GOF_MAX_RECORDS, GOF_MAX_QUANTILES, GOF_TILE, GOF_MAX_BLOCKS, GOF_PART, GOF_OUT = 6, 4096, 1024, 1024, 8, 8
 GOF_UNIFORM, GOF_NORM, GOF_LAPLACE, GOF_T, GOF_GENNORM, GOF_DGAMMA = 0, 1, 2, 3, 4, 5
 GOF_DF_RANGE, GOF_BETA_RANGE, GOF_A_RANGE = (0.1, 1e4), (0.1, 10.0), (0.1, 1e4)
+RAOB_MAX_F, RAOB_TILE_ROWS, RAOB_MAX_BLOCKS, RAOB_SCALARS = 64, 64, 256, 16
+
+
+def raob_state_doubles(F):
+    "SGMCMC_RAOB_STATE_DOUBLES(F)"
+    return RAOB_SCALARS + 2 * F + 4 * F * F
 
 
 class FitGeometry(ctypes.Structure):
@@ -440,6 +446,15 @@ EXPORTS = {
                                              ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "sgmcmc_gof_ppf": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(GofRecord),
                                       ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "sgmcmc_raob_workspace_doubles": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int]),
+    "sgmcmc_raob_gram": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
+                                        ctypes.c_void_p, ctypes.c_void_p]),
+    "sgmcmc_raob_factor": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "sgmcmc_raob_grad": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int]
+                         + [ctypes.c_void_p] * 5),
+    "sgmcmc_raob_predict": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int]
+                            + [ctypes.c_void_p] * 4),
     "sgmcmc_debug_normals": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                             ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64,
                                             ctypes.c_uint32, ctypes.c_void_p]),

@@ -1757,3 +1757,4 @@ int sgmcmc_debug_normals(float* out, int64_t start, int64_t n, uint64_t seed, ui
 // ... and how well the fitted families describe them: distribution functions in log space, KS / CvM / AD, Q-Q (fp64;
 // after fit_hip.inc as well as summary_hip.inc: it uses fit::comp_add and fit::log_gamma)
 #include "gof_hip.inc"
+#include "raob_hip.inc"

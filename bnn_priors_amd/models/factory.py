@@ -3,7 +3,8 @@
 Restates the on-path part of ``bnn_priors/exp_utils.py:63-69,99-105,108-234``:
 ``get_model`` for classificationdensenet / classificationconvnet / googleresnet /
 densenet, the correlated nets correlatedclassificationconvnet / correlatedgoogleresnet, decreasing_mvt_googleresnet and
-the data-driven MNIST convnets datadrivengaussconv / datadrivendoublegammaconv, ``he_initialize``, and the ``net.module.`` wrapper that gives stored
+the data-driven MNIST convnets datadrivengaussconv / datadrivendoublegammaconv, the Rao-Blackwellised regression models
+raobdensenet / raob_linear, ``he_initialize``, and the ``net.module.`` wrapper that gives stored
 samples the reference's key prefix.  (The reference wraps GPU models in
 ``nn.DataParallel``; here one chain owns one GPU, so the wrapper is always the
 plain ``DummyModule`` -- the keys are identical.)
@@ -13,10 +14,10 @@ import math
 import torch
 from torch import nn
 
-from ..prior import get_prior
+from ..prior import LogNormal, get_prior
 from .data_driven import DataDrivenDoubleGammaClassificationConvNet, DataDrivenGaussianClassificationConvNet
 from .nets import (ClassificationConvNet, ClassificationDenseNet, CorrelatedClassificationConvNet, CorrelatedResNet,
-                   DecreasingMVTGoogleResNet, DenseNet, ResNet)
+                   DecreasingMVTGoogleResNet, DenseNet, RaoBDenseNet, RaoBLinearRegression, ResNet)
 
 __all__ = ("get_model", "he_initialize", "DummyModule")
 
@@ -85,6 +86,11 @@ def get_model(x_train, y_train, model, width=50, depth=3, weight_prior="gaussian
         net = DecreasingMVTGoogleResNet(depth=20, bn=batchnorm, softmax_temp=1., **common)
     elif model == "densenet":
         net = DenseNet(x_train.size(-1), y_train.size(-1), width, depth, noise_std=1., **common)
+    elif model == "raobdensenet":
+        # default priors and a learned noise level, whatever the prior arguments say (exp_utils.py:123-124)
+        net = RaoBDenseNet(x_train, y_train, width, noise_std=LogNormal((), -1., 0.2)).to(x_train)
+    elif model == "raob_linear":
+        net = RaoBLinearRegression(x_train, y_train, noise_std=0.5)           # (exp_utils.py:219-220)
     else:
         raise ValueError(f"model='{model}' is outside the accelerated path")
     net = net.to(x_train.device if isinstance(x_train, torch.Tensor) else "cpu")

@@ -1,6 +1,7 @@
 """The three BASELINE networks (gradient providers for the samplers).
 
 * ``ClassificationDenseNet`` -- reference ``models/dense_nets.py:16-67``
+* ``RaoBDenseNet`` / ``RaoBLinearRegression`` -- reference ``models/dense_nets.py:70-87,112-118``
 * ``ClassificationConvNet``  -- reference ``models/conv_nets.py:18-70``
 * ``ResNet`` (googleresnet, depth 6n+2) -- reference ``models/google_resnet.py:11-78``
 * ``CorrelatedClassificationConvNet`` / ``CorrelatedResNet`` -- the same nets with a separate convolution prior
@@ -26,9 +27,10 @@ from .. import conv as _conv
 from .. import pool as _pool
 from .. import prior
 from .. import resblock as _resblock
-from .base import ClassificationModel, RegressionModel
+from .base import ClassificationModel, RaoBRegressionModel, RegressionModel
 
-__all__ = ("Linear", "Conv2d", "LinearPrior", "Conv2dPrior", "DenseNet", "ClassificationDenseNet",
+__all__ = ("Linear", "Conv2d", "LinearPrior", "Conv2dPrior", "DenseNet", "RaoBDenseNet", "RaoBLinearRegression",
+           "ClassificationDenseNet",
            "ClassificationConvNet", "CorrelatedClassificationConvNet", "ResNet", "CorrelatedResNet",
            "DecreasingMVTGoogleResNet", "Reshape")
 
@@ -136,6 +138,23 @@ def DenseNet(in_features, out_features, width, depth=3, noise_std=1.,
     kw = _layer_kwargs(prior_w, loc_w, std_w, prior_b, loc_b, std_b, scaling_fn,
                        weight_prior_params, bias_prior_params)
     return RegressionModel(_dense_stack(in_features, out_features, width, depth, kw), noise_std)
+
+
+def RaoBDenseNet(x_train, y_train, width, noise_std=1., prior_w=prior.Normal, loc_w=0., std_w=2 ** .5,
+                 prior_b=prior.Normal, loc_b=0., std_b=1., scaling_fn=None):
+    """two hidden ReLU layers of ``width`` features whose Normal(0, 2 / width) output layer is integrated out
+    (reference ``models/dense_nets.py:70-87``); width <= 64 for the HIP marginal likelihood"""
+    kw = dict(prior_w=prior_w, loc_w=loc_w, std_w=std_w, prior_b=prior_b, loc_b=loc_b, std_b=std_b,
+              scaling_fn=scaling_fn)
+    net = nn.Sequential(LinearPrior(x_train.size(-1), width, **kw), nn.ReLU(),
+                        LinearPrior(width, width, **kw), nn.ReLU())
+    return RaoBRegressionModel(x_train, y_train, noise_std, last_layer_std=(2 / width) ** .5, net=net)
+
+
+def RaoBLinearRegression(x_train, y_train, noise_std=1., std_w=2 ** .5):
+    "Bayesian linear regression on the inputs themselves (reference ``models/dense_nets.py:112-118``)"
+    return RaoBRegressionModel(x_train, y_train, noise_std, last_layer_std=std_w * x_train.size(-1) ** -.5,
+                               net=nn.Identity())
 
 
 def ClassificationDenseNet(in_features, out_features, width, depth=3, softmax_temp=1.,

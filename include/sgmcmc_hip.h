@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGMCMC_ABI_VERSION 22
+#define SGMCMC_ABI_VERSION 23
 #define SGMCMC_CHUNK 4096 /* default elements per arena chunk = 256 threads x 4 items x 4 elements */
 #define SGMCMC_CHUNK_SMALL 1024 /* small models: one item per thread, 4x more workgroups */
 #define SGMCMC_NSUMS 6
@@ -1494,6 +1494,54 @@ int sgmcmc_gof_statistics(const void* sorted, int is_f64, int64_t n, const sgmcm
 /* Definition 3: model [count][K], empirical [K].  One launch. */
 int sgmcmc_gof_ppf(const void* sorted, int is_f64, int64_t n, const sgmcmc_gof_record* records, int count, int K,
                    double* model, double* empirical, void* stream);
+
+/* ---- The Rao-Blackwellised regression model: marginal likelihood of the last layer integrated out (fp64, deterministic) --
+ * The reference's RaoBRegressionModel (models/base.py:194-311) gives the last layer an iid Normal(0, s2) prior and
+ * integrates it out; what a sampler differentiates is the marginal likelihood below.  This is the definition, restated
+ * in tests/raob_reference.py.  f [N, F] (fp32 or fp64, row-major) are the features of the N training rows, y [N] their
+ * targets, s2 = last_layer_std^2, v = noise_std^2.  All arithmetic is fp64; f and y are widened as they are read.
+ *     G = f^T f,  c = f^T y,  yy = y^T y,  A = s2 G + v I = L L^T,  w = L^-1 c,  b = L^-T w = A^-1 c
+ *     log p(y | f) = -1/2 [N log 2 pi + (N - F) log v + yy / v + 2 sum_a log L_aa - (s2 / v) |w|^2]
+ *     d/df, row n:   -s2 A^-1 f_n + (s2 / v) r_n b,   r_n = y_n - s2 f_n . b
+ *     d/dv:          -1/2 [(N - F) / v - yy / v^2 + |L^-1|_F^2 + (s2 / v^2) |w|^2 + (s2 / v) |b|^2]     (|L^-1|_F^2 = tr A^-1)
+ *     predictive at a row f*:  mean s2 f* . b,  variance v s2 |L^-1 f*|^2 + v  (never below v)
+ * Summation order.  Gram: the rows are cut into tiles of SGMCMC_RAOB_TILE_ROWS; workgroup g of min(tiles,
+ * SGMCMC_RAOB_MAX_BLOCKS) takes tiles g, g + blocks, ...  With y as column F, the lower triangle of order F + 1 is cut
+ * into 4 x 4 blocks, nb = B (B + 1) / 2 of them, B = ceil((F + 1) / 4); a block is cut into S = 256 / nb row slices, slice q
+ * adds rows q, q + S, ... of a tile from 0 by FMA, the tiles' sums are added in ascending order (compensated, Neumaier),
+ * the slices from 0 in ascending order (compensated); the workgroups' partial records -- the packed lower triangle:
+ * G's rows, then c, then yy, (F + 1)(F + 2) / 2 doubles -- are added in ascending order (compensated).  Factor: the
+ * right-looking Cholesky, A_ik -= L_ij L_kj in ascending j, L_ij = A_ij / L_jj, and in the same sweep the forward
+ * substitution X = L^-1: X_jc = X_jc / L_jj, X_ic -= L_ij X_jc in ascending j; multiplication and subtraction are
+ * rounded separately.  w_a = sum_k X_ak c_k, b_a = sum_k X_ka w_k, (A^-1)_ab = sum_k X_ka X_kb, the sums of squares:
+ * from 0 in ascending k, products and sums rounded separately.  The rows' dot products (gradient, predictive) are FMA
+ * chains in ascending k; |L^-1 f*|^2 adds u_a^2 by FMA in 8 chains a = m, m + 8, ... that are added in ascending m.
+ * The STATE RECORD, SGMCMC_RAOB_STATE_DOUBLES(F) doubles: SGMCMC_RAOB_SCALARS scalars {log p, d/dv, v, s2, log det A,
+ * |w|^2 = c^T b, |b|^2, tr A^-1, yy, N, F, 0 ...}, then b [F], L^-1 [F][F], A^-1 [F][F], G [F][F], c [F], L [F][F]
+ * (row-major, the triangles' other halves zero).  A pivot that is not > 0 or not finite makes every entry of the record
+ * NaN except the sums G, c, yy and the sizes; the gradient and the predictive of such a record are NaN.  Nothing traps.
+ * 1 <= N < 2^31, 1 <= F <= SGMCMC_RAOB_MAX_F; anything else or a NULL pointer returns hipErrorInvalidValue and launches
+ * nothing.  The caller provides every buffer; nothing is allocated, nothing synchronises, no atomics. */
+#define SGMCMC_RAOB_MAX_F 64
+#define SGMCMC_RAOB_TILE_ROWS 64
+#define SGMCMC_RAOB_MAX_BLOCKS 256
+#define SGMCMC_RAOB_SCALARS 16
+#define SGMCMC_RAOB_STATE_DOUBLES(F) (SGMCMC_RAOB_SCALARS + 2 * (F) + 4 * (F) * (F))
+/* Doubles of the workspace (the workgroups' partial records) at N rows of F features; -1 when refused.  Host only. */
+int64_t sgmcmc_raob_workspace_doubles(int64_t N, int F);
+/* The Gram pass: one launch that reads f once and writes the partial records. */
+int sgmcmc_raob_gram(const void* f, const void* y, int is_f64, int64_t N, int F, double* workspace, void* stream);
+/* One workgroup: the partials -> the state record.  v is read from noise_var_device [1] (device memory) when that is
+ * not NULL, so that a noise variance that lives on the device never visits the host; else it is noise_var. */
+int sgmcmc_raob_factor(const double* workspace, int64_t N, int F, double last_layer_var, double noise_var,
+                       const double* noise_var_device, double* state, void* stream);
+/* grad_f [N, F] (f's dtype) = upstream d log p / d f and, unless NULL, grad_noise_var [1] = upstream d log p / dv;
+ * upstream [1] is in device memory and of f's dtype (NULL: 1).  One launch. */
+int sgmcmc_raob_grad(const void* f, const void* y, int is_f64, int64_t N, int F, const double* state,
+                     const void* upstream, void* grad_f, double* grad_noise_var, void* stream);
+/* mean [M], var [M] of the predictive at the rows of f_star [M, F] (1 <= M < 2^31).  One launch. */
+int sgmcmc_raob_predict(const void* f_star, int is_f64, int64_t M, int F, const double* state, double* mean,
+                        double* var, void* stream);
 
 /* Test hook: out[i] = spec normal (fp32) of noise index start+i. */
 int sgmcmc_debug_normals(float* out, int64_t start, int64_t n, uint64_t seed, uint32_t stream,
