@@ -24,7 +24,7 @@ INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 SOURCES = [os.path.join(_HERE, "csrc", "sgmcmc_hip.hip")]
 SOURCE = SOURCES[0]
 
-ABI_VERSION = 23
+ABI_VERSION = 24
 CHUNK = 4096
 CHUNK_SMALL = 1024
 NSUMS = 6
@@ -190,6 +190,7 @@ GOF_MAX_RECORDS, GOF_MAX_QUANTILES, GOF_TILE, GOF_MAX_BLOCKS, GOF_PART, GOF_OUT 
 GOF_UNIFORM, GOF_NORM, GOF_LAPLACE, GOF_T, GOF_GENNORM, GOF_DGAMMA = 0, 1, 2, 3, 4, 5
 GOF_DF_RANGE, GOF_BETA_RANGE, GOF_A_RANGE = (0.1, 1e4), (0.1, 10.0), (0.1, 1e4)
 RAOB_MAX_F, RAOB_TILE_ROWS, RAOB_MAX_BLOCKS, RAOB_SCALARS = 64, 64, 256, 16
+TEMPER_SCAN, TEMPER_MAX_LEVELS, TEMPER_UNIFORM_A, TEMPER_UNIFORM_U = 256, 16, 100.0, 0.3
 
 
 def raob_state_doubles(F):
@@ -455,6 +456,15 @@ EXPORTS = {
                          + [ctypes.c_void_p] * 5),
     "sgmcmc_raob_predict": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int]
                             + [ctypes.c_void_p] * 4),
+    "sgmcmc_temper_tails": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
+                                           ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64] + [ctypes.c_void_p] * 3),
+    "sgmcmc_temper_quantile": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                              ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    "sgmcmc_temper_steps": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
+                                           ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_int] + [ctypes.c_void_p] * 5),
+    "sgmcmc_temper_ewma": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
+                                          ctypes.c_int64, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p]),
     "sgmcmc_debug_normals": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
                                             ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64,
                                             ctypes.c_uint32, ctypes.c_void_p]),

@@ -1757,4 +1757,7 @@ int sgmcmc_debug_normals(float* out, int64_t start, int64_t n, uint64_t seed, ui
 // ... and how well the fitted families describe them: distribution functions in log space, KS / CvM / AD, Q-Q (fp64;
 // after fit_hip.inc as well as summary_hip.inc: it uses fit::comp_add and fit::log_gamma)
 #include "gof_hip.inc"
+// ... and whether a chain samples at its temperature: chi-square tails at any size, intervals, coverage, EWMA (fp64;
+// after gof_hip.inc: it uses gof::stirling_rest, summary::log1p_minus and fit::comp_add)
+#include "temper_hip.inc"
 #include "raob_hip.inc"

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGMCMC_ABI_VERSION 23
+#define SGMCMC_ABI_VERSION 24
 #define SGMCMC_CHUNK 4096 /* default elements per arena chunk = 256 threads x 4 items x 4 elements */
 #define SGMCMC_CHUNK_SMALL 1024 /* small models: one item per thread, 4x more workgroups */
 #define SGMCMC_NSUMS 6
@@ -1542,6 +1542,51 @@ int sgmcmc_raob_grad(const void* f, const void* y, int is_f64, int64_t N, int F,
 /* mean [M], var [M] of the predictive at the rows of f_star [M, F] (1 <= M < 2^31).  One launch. */
 int sgmcmc_raob_predict(const void* f_star, int is_f64, int64_t M, int F, const double* state, double* mean,
                         double* var, void* stream);
+
+/* ---- Sampler temperature diagnostics: chi-square laws of the kinetic temperatures (fp64, deterministic) ---------------
+ * A parameter tensor with d elements has kinetic temperature estimate T^ with T^ / T ~ chi^2_d / d at the target T (the
+ * reference reads them off plots: bnn_priors/plot.py:14-141).  With a = d / 2 and r = T^ / T the distribution function is
+ * the regularised incomplete gamma function P(a, a r), Q = 1 - P.  d is an integer in [1, 2^31 - 1]; a d outside it gives
+ * NaN.  Restated at 50 digits in tests/temperature_reference.py; the methods, their switch points
+ * (SGMCMC_TEMPER_UNIFORM_A, SGMCMC_TEMPER_UNIFORM_U) and the measured error on each side are in csrc/temper_hip.inc.
+ *  1. Tails.  est [S, K] (fp32 or fp64, element (s, k) at s * stride_s + k * stride_k), r = est / temperature[s *
+ *     temp_stride] (temperature in device memory; temp_stride = 0 for one value; NULL: r = est), sizes [K] int64 in device
+ *     memory.  out [4][S * K]: P, Q, log P, log Q.  One of the two tails is evaluated in log space and the other derived
+ *     from it; r <= 0 gives P = 0, r = inf gives Q = 0, NaN gives NaN.
+ *  2. Quantiles.  out [K][M]: the r at which the tail (upper[m] ? Q : P) of tensor k equals value[m] (its logarithm when
+ *     is_log): Newton steps on the log-tail from the Wilson-Hilferty point inside a bracket, 100 at most.  value, upper in
+ *     device memory.  A value outside [0, 1] gives NaN, 0 and 1 the ends 0 and inf.
+ *  3. The step table.  bounds [K][C][2] (lower, upper), C <= SGMCMC_TEMPER_MAX_LEVELS.  share [C][S]: the number of
+ *     tensors with lower <= r <= upper, both ends included, NaN and inf outside, divided by K.  totals [K * C + 1] int64:
+ *     per tensor and level the number of steps inside, then the number of finite r: integer counts, exact in any order.
+ *     Workgroup b of min(ceil(S / 256), 256) takes the tiles of 256 steps b, b + blocks, ...; its counts are gathered in
+ *     LDS (K * C + 1 <= 4096; else in memory directly) and added to totals by integer atomics.
+ *     mean [S], se [S]: with w = sizes and x = est (NOT divided by the temperature), Cochran's (1977) weighted mean
+ *     xw = sum w x / sum w and se = K / ((K - 1) (sum w)^2) [sum (w x - wb xw)^2 - 2 xw sum (w x - wb xw)(w - wb)
+ *     + xw^2 sum (w - wb)^2], wb = sum w / K.  The bracket equals sum w^2 (x - xw)^2 identically and is evaluated in
+ *     that form (the three terms cancel); every sum runs over k ascending, compensated (Neumaier).  C = 0 computes
+ *     mean and se only (temperature, bounds, share, totals unused); mean = se = NULL computes the coverage only.
+ *  4. EWMA.  x [R, S] strided, y [R][S]: y_0 = x_0, y_t = (1 - alpha) x_t + alpha y_(t-1), 0 <= alpha < 1, products and
+ *     sum rounded separately.  One workgroup per row; thread t of SGMCMC_TEMPER_SCAN owns the L = ceil(S / SCAN) steps
+ *     from t L on, composes their affine maps in order, the composites are scanned (Hillis-Steele) and the steps replayed
+ *     from the carry.  alpha = 0 copies the input's bits; a NaN poisons what follows it in its own row and nothing else;
+ *     +-inf stays +-inf in what follows it, as step by step (also where alpha^L underflows).
+ * 1 <= S, S * K <= 2^31 - 1 (S * R for the EWMA); anything else or a missing pointer returns hipErrorInvalidValue and
+ * launches nothing.  The caller provides every buffer; nothing is allocated, nothing synchronises, and the only atomics
+ * are the integer counts of 3. */
+#define SGMCMC_TEMPER_SCAN 256
+#define SGMCMC_TEMPER_MAX_LEVELS 16
+#define SGMCMC_TEMPER_UNIFORM_A 100.0
+#define SGMCMC_TEMPER_UNIFORM_U 0.3
+int sgmcmc_temper_tails(const void* est, int is_f64, int64_t S, int K, int64_t stride_s, int64_t stride_k,
+                        const double* temperature, int64_t temp_stride, const int64_t* sizes, double* out, void* stream);
+int sgmcmc_temper_quantile(const int64_t* sizes, int K, const double* value, const int32_t* upper, int M, int is_log,
+                           double* out, void* stream);
+int sgmcmc_temper_steps(const void* est, int is_f64, int64_t S, int K, int64_t stride_s, int64_t stride_k,
+                        const double* temperature, int64_t temp_stride, const int64_t* sizes, const double* bounds, int C,
+                        double* share, double* mean, double* se, int64_t* totals, void* stream);
+int sgmcmc_temper_ewma(const void* x, int is_f64, int R, int64_t S, int64_t stride_r, int64_t stride_s, double alpha,
+                       double* y, void* stream);
 
 /* Test hook: out[i] = spec normal (fp32) of noise index start+i. */
 int sgmcmc_debug_normals(float* out, int64_t start, int64_t n, uint64_t seed, uint32_t stream,
