@@ -1102,14 +1102,14 @@ __device__ __forceinline__ double prior_log_norm(const sgmcmc_segment& s, double
   return 0.0;
 }
 
-// SGMCMC_PRIOR_FILTER_WHITENED (include/sgmcmc_hip.h): this chunk's elements of segment s.  Element j of the segment
-// belongs to filter f = j / P at position q = j mod P; it re-reads its filter's P values from theta (a filter straddles
-// chunk boundaries: P does not divide the chunk), whitens them, z = (theta_f - mu) W, and adds
-// -(1/N) sum_k psi(z_k) W[q][k] to g[j] -- everything in fp64, one rounding into g.  The log-density partial is
-// base(z_q) + lognorm / P, so the P elements of a filter together carry its whole log-density.  base / psi per
-// SGMCMC_FILTER_BASE_* (include/sgmcmc_hip.h): psi = 0 at z == 0 for every base.  W and mu are staged in
-// LDS (uniform reads); the P values of the filter live in registers (P <= SGMCMC_FILTER_MAX_P).
-// (sW [SGMCMC_FILTER_MAX_P^2] and smu [SGMCMC_FILTER_MAX_P] are the caller's LDS, shared with the multivariate-t branch)
+// The two whitened kinds, SGMCMC_PRIOR_FILTER_WHITENED and SGMCMC_PRIOR_MULTIVARIATE_T (include/sgmcmc_hip.h).  Element j
+// of a segment belongs to the filter of P elements that begins at j - q, q = j mod P; it re-reads its filter's P values
+// from theta (a filter straddles chunk boundaries: P does not divide the chunk), whitens them, z = (theta_f - mu) W, and
+// adds -(1/N) coef sum_k psi(z_k) W[q][k] to g[j] -- everything in fp64, one rounding into g.  W and mu are staged in LDS
+// (uniform reads); the P values of the filter live in registers (P <= SGMCMC_FILTER_MAX_P).
+constexpr int kMaxP = SGMCMC_FILTER_MAX_P;
+
+// (sW [kMaxP^2] and smu [kMaxP] are the caller's LDS)
 __device__ __forceinline__ void stage_whitening(const sgmcmc_filter_prior* __restrict__ fp, double* sW, double* smu) {
   const int P = fp->P;
   for (int i = threadIdx.x; i < P * P; i += kThreads) sW[i] = fp->W[i];
@@ -1117,16 +1117,89 @@ __device__ __forceinline__ void stage_whitening(const sgmcmc_filter_prior* __res
   __syncthreads();
 }
 
+// d_i = theta_f[i] - mu_i of the filter at f0
 template <typename T>
-__device__ __forceinline__ void filter_prior_chunk(const sgmcmc_layout& L, const ChunkCtx& cx,
-                                                   const sgmcmc_segment* __restrict__ sp, double num_data,
-                                                   bool calc_logp, double& lp, double* sW, double* smu) {
-  constexpr int kMaxP = SGMCMC_FILTER_MAX_P;
+__device__ __forceinline__ void load_filter(double (&d)[kMaxP], const T* __restrict__ th, int64_t f0,
+                                            const double* smu, int P) {
+#pragma unroll
+  for (int i = 0; i < kMaxP; ++i)
+    if (i < P) d[i] = (double)th[f0 + i] - smu[i];
+}
+
+// z_k = (d W)_k -- fp64, fixed order
+__device__ __forceinline__ double whitened_at(const double (&d)[kMaxP], const double* sW, int P, int k) {
+  double z = 0.0;
+#pragma unroll
+  for (int i = 0; i < kMaxP; ++i)
+    if (i < P) z = fma(d[i], sW[i * P + k], z);
+  return z;
+}
+
+// FILTER_WHITENED: psi = d base / dz per SGMCMC_FILTER_BASE_* (0 at z == 0 for every base), the factor is exactly 1, and
+// position q adds base(z_q) + lognorm / P, so the P elements of a filter together carry its whole log-density.
+struct FilterKind {
+  int base;
+  double beta, inv_bs, ln_pos;
+  __device__ __forceinline__ FilterKind(const sgmcmc_filter_prior* __restrict__ fp)
+      : base(fp->base), beta(fp->beta), inv_bs(1.0 / fp->base_scale), ln_pos(fp->lognorm / (double)fp->P) {}
+  // (own: k == q on a step that wants the log-density)
+  __device__ __forceinline__ double psi(double z, bool own, double& lp) const {
+    double dz, b = 0.0;
+    switch (base) {
+      case SGMCMC_FILTER_BASE_NORMAL:
+        dz = -z;
+        b = -0.5 * z * z;
+        break;
+      case SGMCMC_FILTER_BASE_GENNORM: {
+        const double a = fabs(z) * inv_bs;
+        dz = z == 0.0 ? 0.0 : -copysign(beta * inv_bs * pow_noinline(a, beta - 1.0), z);
+        if (own) b = -pow_noinline(a, beta);
+        break;
+      }
+      case SGMCMC_FILTER_BASE_LAPLACE:        // b = base_scale
+        dz = z == 0.0 ? 0.0 : -copysign(inv_bs, z);
+        b = -fabs(z) * inv_bs;
+        break;
+      case SGMCMC_FILTER_BASE_DOUBLE_GAMMA:   // c = beta, rate = 1 / base_scale
+        dz = z == 0.0 ? 0.0 : (beta - 1.0) / z - copysign(inv_bs, z);
+        // (beta - 1) log|z| as torch's xlogy: 0 when beta == 1, +-inf at z == 0 otherwise
+        if (own) b = (beta == 1.0 ? 0.0 : (beta - 1.0) * log(fabs(z))) - fabs(z) * inv_bs;
+        break;
+      default:                                // unknown base: poison, never a silent Normal
+        dz = b = __builtin_nan("");
+    }
+    if (own) lp += b + ln_pos;
+    return dz;
+  }
+  __device__ __forceinline__ double coef(int64_t, bool, double&) const { return 1.0; }
+};
+
+// MULTIVARIATE_T, after mvt_event_kernel: psi = z, the factor is -(df + D) / (lambda + M_e) of the element's event, and
+// the event's first element adds its whole log-density (so the segment's chunk partials hold each event exactly once).
+struct MvtKind {
+  double lam, c, lognorm;
+  int64_t ev_div, ev_mod;
+  const double* __restrict__ msum;
+  __device__ __forceinline__ MvtKind(const sgmcmc_filter_prior* __restrict__ fp)
+      : lam(fp->df - 2.0), c(fp->df + (double)fp->ev_size), lognorm(fp->lognorm), ev_div(fp->ev_div),
+        ev_mod(fp->ev_mod), msum(fp->ev_sum) {}
+  __device__ __forceinline__ double psi(double z, bool, double&) const { return z; }
+  __device__ __forceinline__ double coef(int64_t e, bool calc_logp, double& lp) const {
+    const double M = msum[(e / ev_div) % ev_mod];
+    if (calc_logp && e < ev_div * ev_mod && e % ev_div == 0) lp += lognorm - 0.5 * c * log1p(M / lam);
+    return -c / (lam + M);
+  }
+};
+
+// this chunk's elements of the whitened segment sp: g_e = (T)(g_e - (coef sum_k psi(z_k) W[q][k]) / N)
+template <typename T, typename Kind>
+__device__ __forceinline__ void whitened_chunk(const sgmcmc_layout& L, const ChunkCtx& cx,
+                                               const sgmcmc_segment* __restrict__ sp, double num_data,
+                                               bool calc_logp, double& lp, double* sW, double* smu) {
   const sgmcmc_filter_prior* __restrict__ fp = L.filters + cx.seg;
   const int P = fp->P;
   stage_whitening(fp, sW, smu);
-  const int base = fp->base;
-  const double beta = fp->beta, inv_bs = 1.0 / fp->base_scale, ln_pos = fp->lognorm / (double)P;
+  const Kind kind(fp);
   const double inv_n = 1.0 / num_data;
   const T* __restrict__ th = (const T*)sp->theta;
   T* __restrict__ gp = (T*)sp->g;
@@ -1136,65 +1209,16 @@ __device__ __forceinline__ void filter_prior_chunk(const sgmcmc_layout& L, const
 #pragma unroll 1
     for (int l = 0; l < 4; ++l) {
       if (j0 + l >= cx.n_valid) break;
-      const int64_t e = cx.seg_off + j0 + l;      // element of the segment; its filter is [f0, f0 + P) (numel % P == 0)
+      const int64_t e = cx.seg_off + j0 + l;      // element of the segment; its filter begins at e - q (numel % P == 0)
       const int q = (int)(e % P);
-      const int64_t f0 = e - q;
       double d[kMaxP];
-#pragma unroll
-      for (int i = 0; i < kMaxP; ++i)
-        if (i < P) d[i] = (double)th[f0 + i] - smu[i];
+      load_filter<T>(d, th, e - q, smu, P);
       double gs = 0.0;
-      for (int k = 0; k < P; ++k) {
-        double z = 0.0;
-#pragma unroll
-        for (int i = 0; i < kMaxP; ++i)
-          if (i < P) z = fma(d[i], sW[i * P + k], z);
-        double psi, b = 0.0;
-        switch (base) {
-          case SGMCMC_FILTER_BASE_NORMAL:
-            psi = -z;
-            b = -0.5 * z * z;
-            break;
-          case SGMCMC_FILTER_BASE_GENNORM: {
-            const double a = fabs(z) * inv_bs;
-            psi = z == 0.0 ? 0.0 : -copysign(beta * inv_bs * pow_noinline(a, beta - 1.0), z);
-            if (calc_logp && k == q) b = -pow_noinline(a, beta);
-            break;
-          }
-          case SGMCMC_FILTER_BASE_LAPLACE:        // b = base_scale
-            psi = z == 0.0 ? 0.0 : -copysign(inv_bs, z);
-            b = -fabs(z) * inv_bs;
-            break;
-          case SGMCMC_FILTER_BASE_DOUBLE_GAMMA:   // c = beta, rate = 1 / base_scale
-            psi = z == 0.0 ? 0.0 : (beta - 1.0) / z - copysign(inv_bs, z);
-            // (beta - 1) log|z| as torch's xlogy: 0 when beta == 1, +-inf at z == 0 otherwise
-            if (calc_logp && k == q) b = (beta == 1.0 ? 0.0 : (beta - 1.0) * log(fabs(z))) - fabs(z) * inv_bs;
-            break;
-          default:                                // unknown base: poison, never a silent Normal
-            psi = b = __builtin_nan("");
-        }
-        gs = fma(psi, sW[q * P + k], gs);
-        if (calc_logp && k == q) lp += b + ln_pos;
-      }
-      gp[e] = (T)((double)gp[e] - gs * inv_n);
+      for (int k = 0; k < P; ++k)
+        gs = fma(kind.psi(whitened_at(d, sW, P, k), calc_logp && k == q, lp), sW[q * P + k], gs);
+      gp[e] = (T)((double)gp[e] - (kind.coef(e, calc_logp, lp) * gs) * inv_n);
     }
   }
-}
-
-// (d_i = theta_f[i] - mu_i of one filter)  sum_k z_k W[q][k] with z = d W, and |z|^2 -- fp64, fixed order
-template <int kMaxP>
-__device__ __forceinline__ double whitened_row(const double (&d)[kMaxP], const double* sW, int P, int q, double* zz) {
-  double gs = 0.0, ss = 0.0;
-  for (int k = 0; k < P; ++k) {
-    double z = 0.0;
-#pragma unroll
-    for (int i = 0; i < kMaxP; ++i)
-      if (i < P) z = fma(d[i], sW[i * P + k], z);
-    if (q >= 0) gs = fma(z, sW[q * P + k], gs);
-    ss = fma(z, z, ss);
-  }
-  if (zz) *zz = ss;
-  return gs;
 }
 
 // SGMCMC_PRIOR_MULTIVARIATE_T, first launch of sgmcmc_prior_grad: the kMvtEventGroups workgroups (s, y) compute
@@ -1208,7 +1232,6 @@ __device__ __forceinline__ double whitened_row(const double (&d)[kMaxP], const d
 constexpr int kMvtEventGroups = 8;
 template <typename T>
 __global__ __launch_bounds__(kThreads) void mvt_event_kernel(sgmcmc_layout L) {
-  constexpr int kMaxP = SGMCMC_FILTER_MAX_P;
   __shared__ double sW[kMaxP * kMaxP], smu[kMaxP];
   const sgmcmc_segment* __restrict__ sp = &L.segs[blockIdx.x];
   if (sp->prior_kind != SGMCMC_PRIOR_MULTIVARIATE_T || sp->g == nullptr) return;     // (uniform over the workgroup)
@@ -1224,57 +1247,18 @@ __global__ __launch_bounds__(kThreads) void mvt_event_kernel(sgmcmc_layout L) {
   for (int64_t e = (int64_t)blockIdx.y * (kThreads / 64) + wave; e < ev_mod; e += kMvtEventGroups * (kThreads / 64)) {
     double acc = 0.0;
     for (int64_t f = lane; f < n_filt; f += 64) {
-      const int64_t f0 = (f / per_run) * stride + e * ev_div + (f % per_run) * P;
       double d[kMaxP];
-#pragma unroll
-      for (int i = 0; i < kMaxP; ++i)
-        if (i < P) d[i] = (double)th[f0 + i] - smu[i];
-      double ss;
-      whitened_row<kMaxP>(d, sW, P, -1, &ss);
+      load_filter<T>(d, th, (f / per_run) * stride + e * ev_div + (f % per_run) * P, smu, P);
+      double ss = 0.0;
+      for (int k = 0; k < P; ++k) {
+        const double z = whitened_at(d, sW, P, k);
+        ss = fma(z, z, ss);
+      }
       acc += ss;
     }
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 64);
     if (lane == 0) out[e] = acc;
-  }
-}
-
-// SGMCMC_PRIOR_MULTIVARIATE_T, in the full prior kernel after mvt_event_kernel: element j of filter f0 (q = j mod P) of
-// event e gets g_j -= (1/N) (-(df + D) / (lambda + M_e)) (z W^T)_q, all fp64, one rounding into g.  The event's first
-// element adds its whole log-density (so the segment's chunk partials hold each event exactly once).
-template <typename T>
-__device__ __forceinline__ void mvt_prior_chunk(const sgmcmc_layout& L, const ChunkCtx& cx,
-                                                const sgmcmc_segment* __restrict__ sp, double num_data,
-                                                bool calc_logp, double& lp, double* sW, double* smu) {
-  constexpr int kMaxP = SGMCMC_FILTER_MAX_P;
-  const sgmcmc_filter_prior* __restrict__ fp = L.filters + cx.seg;
-  const int P = fp->P;
-  stage_whitening(fp, sW, smu);
-  const double lam = fp->df - 2.0, c = fp->df + (double)fp->ev_size, lognorm = fp->lognorm;
-  const int64_t ev_div = fp->ev_div, ev_mod = fp->ev_mod, first_end = ev_div * ev_mod;
-  const double* __restrict__ msum = fp->ev_sum;
-  const double inv_n = 1.0 / num_data;
-  const T* __restrict__ th = (const T*)sp->theta;
-  T* __restrict__ gp = (T*)sp->g;
-  for (int it = 0; it < items_of(L); ++it) {
-    const int j0 = (it * kThreads + threadIdx.x) * 4;
-    if (j0 >= cx.n_valid) break;
-#pragma unroll 1
-    for (int l = 0; l < 4; ++l) {
-      if (j0 + l >= cx.n_valid) break;
-      const int64_t e = cx.seg_off + j0 + l;
-      const int q = (int)(e % P);
-      const int64_t f0 = e - q;
-      double d[kMaxP];
-#pragma unroll
-      for (int i = 0; i < kMaxP; ++i)
-        if (i < P) d[i] = (double)th[f0 + i] - smu[i];
-      const double gs = whitened_row<kMaxP>(d, sW, P, q, nullptr);
-      const double M = msum[(e / ev_div) % ev_mod];
-      const double coef = -c / (lam + M);
-      gp[e] = (T)((double)gp[e] - coef * gs * inv_n);
-      if (calc_logp && e < first_end && e % ev_div == 0) lp += lognorm - 0.5 * c * log1p(M / lam);
-    }
   }
 }
 
@@ -1291,11 +1275,11 @@ __device__ __forceinline__ void prior_body(const sgmcmc_layout& L, double num_da
   double acc[2] = {0.0, 0.0};   // log-density partial; d/dscale of it (hierarchical scales)
   if (FULL && (sp->prior_kind == SGMCMC_PRIOR_FILTER_WHITENED || sp->prior_kind == SGMCMC_PRIOR_MULTIVARIATE_T)) {
     // (segment-level branches: the record is read only here; sgmcmc_prior_grad launches this kernel for such tables)
-    constexpr int kMaxP = SGMCMC_FILTER_MAX_P;
     __shared__ double sW[kMaxP * kMaxP], smu[kMaxP];
     if (sp->g != nullptr) {
-      if (sp->prior_kind == SGMCMC_PRIOR_FILTER_WHITENED) filter_prior_chunk<T>(L, cx, sp, num_data, calc_logp, acc[0], sW, smu);
-      else mvt_prior_chunk<T>(L, cx, sp, num_data, calc_logp, acc[0], sW, smu);
+      if (sp->prior_kind == SGMCMC_PRIOR_FILTER_WHITENED)
+        whitened_chunk<T, FilterKind>(L, cx, sp, num_data, calc_logp, acc[0], sW, smu);
+      else whitened_chunk<T, MvtKind>(L, cx, sp, num_data, calc_logp, acc[0], sW, smu);
     }
   } else if ((sp->prior_kind != SGMCMC_PRIOR_NONE || parts) && sp->g != nullptr) {
     T* __restrict__ gp = (T*)sp->g + cx.seg_off;

@@ -252,8 +252,8 @@ class Engine:
     def set_priors(self, specs, links=None, filters=None):
         """specs[i] = None or (kind, loc, scale, shape-parameter): enable the in-kernel prior gradient;
         links[i] = index of the hyper segment whose VALUE is segment i's scale (hierarchical priors), or None;
-        filters[i] = the whitening of a PRIOR_FILTER_WHITENED segment (``Prior.fused_filter_spec()``) or the table of a
-        PRIOR_MULTIVARIATE_T one (``Prior.fused_mvt_spec()``), or None"""
+        filters[i] = the table of a PRIOR_FILTER_WHITENED or PRIOR_MULTIVARIATE_T segment (``Prior.fused_table()``: its
+        ``kind`` says which), or None"""
         self._set_filters(specs, filters)
         self.prior_links = False
         for i, sp in enumerate(specs):
@@ -285,19 +285,18 @@ class Engine:
             self.layout.filters = None
             return
         host = np.zeros(self.n_seg, dtype=_hip.FILTER_DTYPE)
-        mvt = [i for i, f in enumerate(filters) if f is not None and int(specs[i][0]) == _hip.PRIOR_MULTIVARIATE_T]
-        n_events = sum(int(filters[i]["ev_mod"]) for i in mvt)
-        if mvt and (self._event_sums is None or self._event_sums.numel() < n_events):
+        n_events = sum(int(f["ev_mod"]) for f in filters if f is not None and f["kind"] == _hip.PRIOR_MULTIVARIATE_T)
+        if n_events and (self._event_sums is None or self._event_sums.numel() < n_events):
             # the events' Mahalanobis sums (scratch of sgmcmc_prior_grad); kept while large enough, so that the records'
             # pointers into it -- and graphs captured with them -- stay valid across set_priors
             self._event_sums = torch.zeros(n_events, dtype=torch.float64, device=self.device)
         base = 0
         for i, f in enumerate(filters):
             if f is not None:
-                assert specs[i] is not None and int(specs[i][0]) in (_hip.PRIOR_FILTER_WHITENED, _hip.PRIOR_MULTIVARIATE_T)
+                assert specs[i] is not None and int(specs[i][0]) == f["kind"]
                 self._filter_row(host[i], i, f)
-                if i in mvt:
-                    self._mvt_row(host[i], i, f, self._event_sums.data_ptr() + 8 * base)
+                if f["kind"] == _hip.PRIOR_MULTIVARIATE_T:
+                    host[i]["ev_sum"] = self._event_sums.data_ptr() + 8 * base
                     base += int(f["ev_mod"])
         self.filter_host = host
         if self._filter_dev is None or self._filter_dev.numel() != host.nbytes:
@@ -306,15 +305,24 @@ class Engine:
         self.layout.filters = self._filter_dev.data_ptr()
 
     def _filter_row(self, row, i, f):
-        P = int(f["P"])
+        "validate the table f of segment i and fill its record by ``f['kind']`` (ev_sum, the engine's scratch, is not f's)"
+        assert f["kind"] in (_hip.PRIOR_FILTER_WHITENED, _hip.PRIOR_MULTIVARIATE_T)
+        P, n = int(f["P"]), self.params[i].numel()
         W, mu = np.asarray(f["W"], dtype=np.float64), np.asarray(f["mu"], dtype=np.float64)
-        if not 1 <= P <= _hip.FILTER_MAX_P or W.shape != (P, P) or mu.shape != (P,) or self.params[i].numel() % P:
+        if not 1 <= P <= _hip.FILTER_MAX_P or W.shape != (P, P) or mu.shape != (P,) or n % P:
             raise ValueError(f"segment {i}: a filter prior needs 1 <= P <= {_hip.FILTER_MAX_P} positions, a P x P "
                              f"whitening and P locations, and a multiple of P elements (P = {P})")
         base = int(f.get("base", _hip.FILTER_BASE_NORMAL))
         if base not in (_hip.FILTER_BASE_NORMAL, _hip.FILTER_BASE_GENNORM, _hip.FILTER_BASE_LAPLACE,
                         _hip.FILTER_BASE_DOUBLE_GAMMA):
             raise ValueError(f"segment {i}: unknown filter base density {base}")
+        if f["kind"] == _hip.PRIOR_MULTIVARIATE_T:
+            D, div, mod = int(f["ev_size"]), int(f["ev_div"]), int(f["ev_mod"])
+            if not (float(f["df"]) > 2 and D % P == 0 and div % P == 0 and mod >= 1 and n % (div * mod) == 0
+                    and D * mod == n):
+                raise ValueError(f"segment {i}: a multivariate-t prior needs df > 2 and events of whole filters that tile "
+                                 f"the tensor (P = {P}, D = {D}, ev_div = {div}, ev_mod = {mod}, numel = {n})")
+            row["df"], row["ev_size"], row["ev_div"], row["ev_mod"] = float(f["df"]), D, div, mod
         row["P"], row["base"] = P, base
         row["beta"], row["base_scale"] = float(f.get("beta", 2.0)), float(f.get("base_scale", 1.0))
         row["lognorm"] = float(f["lognorm"])
@@ -323,19 +331,10 @@ class Engine:
         row["mu"][:P] = mu
         row["W"][:P * P] = W.reshape(-1)
 
-    def _mvt_row(self, row, i, f, sums_ptr):
-        P, D, div, mod, n = int(f["P"]), int(f["ev_size"]), int(f["ev_div"]), int(f["ev_mod"]), self.params[i].numel()
-        if not (float(f["df"]) > 2 and D % P == 0 and div % P == 0 and mod >= 1 and n % (div * mod) == 0
-                and D * mod == n):
-            raise ValueError(f"segment {i}: a multivariate-t prior needs df > 2 and events of whole filters that tile "
-                             f"the tensor (P = {P}, D = {D}, ev_div = {div}, ev_mod = {mod}, numel = {n})")
-        row["df"], row["ev_size"], row["ev_div"], row["ev_mod"], row["ev_sum"] = float(f["df"]), D, div, mod, sums_ptr
-
     def update_filter(self, i, f):
-        """rewrite segment i's whitening in place (``ConvCovariance.assign_cov``): the device buffer keeps its
-        address, so captured graphs read the new record at their next replay"""
-        row = self.filter_host[i]
-        self._filter_row(row, i, f)
+        """rewrite segment i's table in place (``ConvCovariance.assign_cov``): the device buffer keeps its address, so
+        captured graphs read the new record at their next replay"""
+        self._filter_row(self.filter_host[i], i, f)
         n = _hip.FILTER_DTYPE.itemsize
         self._filter_dev[i * n:(i + 1) * n].copy_(torch.from_numpy(self.filter_host[i:i + 1].view(np.uint8).copy()))
 

@@ -212,25 +212,20 @@ class SGLD(torch.optim.Optimizer):
                 specs[i] = None
                 continue
             links[i] = claimed[h] = h
-        # multivariate priors over each convolution filter's positions with a fixed whitening (prior/correlated.py):
-        # one segment-level kind of the same launch (SGMCMC_PRIOR_FILTER_WHITENED)
+        # the segment-level kinds of the same launch, each with a table of its own: a fixed whitening of every convolution
+        # filter's positions (prior/correlated.py, SGMCMC_PRIOR_FILTER_WHITENED) and the multivariate Student-t, which
+        # adds one reduction per event in a launch before the prior kernel (prior/multivariate_t.py)
         filters = [None] * len(specs)
         for i, pr in enumerate(priors):
             if pr is not None and specs[i] is None:
-                filters[i] = pr.fused_filter_spec()
+                filters[i] = pr.fused_table()
                 if filters[i] is not None:
-                    specs[i] = (_hip.PRIOR_FILTER_WHITENED, 0.0, 1.0, 0.0)
-                    continue
-                # multivariate Student-t (prior/multivariate_t.py): the same whitening plus one reduction per event,
-                # a launch of its own before the prior kernel (SGMCMC_PRIOR_MULTIVARIATE_T)
-                filters[i] = pr.fused_mvt_spec()
-                if filters[i] is not None:
-                    specs[i] = (_hip.PRIOR_MULTIVARIATE_T, 0.0, 1.0, 0.0)
+                    specs[i] = (filters[i]["kind"], 0.0, 1.0, 0.0)
         leftover = [pr for pr, sp in zip(priors, specs) if pr is not None and sp is None]
         leftover.extend(by_param.values())   # priors whose .p this optimizer does not own
         eng.set_priors(specs, links, filters)
         for i, f in enumerate(filters):
-            if f is not None and specs[i][0] == _hip.PRIOR_FILTER_WHITENED:
+            if f is not None:
                 priors[i].bind_fused_filter(eng, i)     # ConvCovariance.assign_cov rewrites the record in place
         self._hyper_params = [eng.params[h] for h in sorted(claimed)]
         self._hyper_grads = [torch.zeros_like(p) for p in self._hyper_params]

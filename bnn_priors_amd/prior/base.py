@@ -105,16 +105,21 @@ class Prior(nn.Module):
 
     def fused_filter_spec(self):
         """The whitening of a multivariate prior over each convolution filter's ``P = kh * kw`` positions that the HIP
-        hook evaluates as SGMCMC_PRIOR_FILTER_WHITENED (include/sgmcmc_hip.h), computed in float64: a dict with ``P``,
-        ``base`` (_hip.FILTER_BASE_*), ``beta``, ``base_scale``, ``lognorm``, ``mu`` [P] and ``W`` [P, P] such that
-        ``log p(theta_f) = sum_k base((theta_f - mu) W)_k + lognorm``.  None when the prior is not such a family or
-        any of its arguments is learnable (prior/correlated.py)"""
+        hook evaluates as SGMCMC_PRIOR_FILTER_WHITENED (include/sgmcmc_hip.h), computed in float64: a dict with ``kind``
+        (_hip.PRIOR_FILTER_WHITENED), ``P``, ``base`` (_hip.FILTER_BASE_*), ``beta``, ``base_scale``, ``lognorm``, ``mu`` [P]
+        and ``W`` [P, P] such that ``log p(theta_f) = sum_k base((theta_f - mu) W)_k + lognorm``.  None when the prior is
+        not such a family or any of its arguments is learnable (prior/correlated.py)"""
         return None
 
     def fused_mvt_spec(self):
         """The table of a multivariate Student-t prior that the HIP hook evaluates as SGMCMC_PRIOR_MULTIVARIATE_T
-        (prior/multivariate_t.py), or None"""
+        (prior/multivariate_t.py; its ``kind`` is _hip.PRIOR_MULTIVARIATE_T), or None"""
         return None
+
+    def fused_table(self):
+        "the segment-level table the HIP hook takes for this prior: whichever of the two above is not None (else None)"
+        spec = self.fused_filter_spec()
+        return spec if spec is not None else self.fused_mvt_spec()
 
     def bind_fused_filter(self, engine, index):
         "``engine.update_filter(index, ...)`` whenever this prior's whitening changes (``refresh_fused_filter``)"
@@ -125,12 +130,14 @@ class Prior(nn.Module):
         live = []
         for ref, index in _FILTER_SINKS.get(self, ()):
             eng = ref()
-            if (eng is None or getattr(eng, "filter_host", None) is None
-                    or int(eng.seg_host[index]["prior_kind"]) != 10):       # (SGMCMC_PRIOR_FILTER_WHITENED)
+            # (gone, or its priors have been set anew and the segment holds no record any more: P == 0)
+            if eng is None or getattr(eng, "filter_host", None) is None or not eng.filter_host[index]["P"]:
                 continue
-            spec = self.fused_filter_spec()
+            spec = self.fused_table()
             if spec is None:
                 raise RuntimeError("a prior fused as a filter prior no longer has a fixed whitening")
+            if int(eng.seg_host[index]["prior_kind"]) != spec["kind"]:
+                continue
             eng.update_filter(index, spec)
             live.append((ref, index))
         if self in _FILTER_SINKS:

@@ -21,6 +21,7 @@ import torch
 import torch.distributions as td
 from torch import nn
 
+from .. import _hip
 from .base import Prior
 from .distributions import DoubleGamma, GeneralizedNormal
 
@@ -29,7 +30,6 @@ __all__ = ("ConvCorrelatedNormal", "ConvCorrNormalGamma", "ConvCovariance", "Fix
 
 
 _LOG_2PI = float(np.log(2.0 * np.pi))
-_FILTER_BASE_LAPLACE, _FILTER_BASE_DOUBLE_GAMMA = 2, 3        # (_hip.FILTER_BASE_*: the package imports without the library)
 
 
 def _fixed(v):
@@ -47,7 +47,7 @@ def _filter_positions(prior):
     if p.dim() < 2 or not p.is_contiguous():
         return None
     P = p.shape[-2] * p.shape[-1]
-    return P if 1 <= P <= 25 else None            # (SGMCMC_FILTER_MAX_P)
+    return P if 1 <= P <= _hip.FILTER_MAX_P else None
 
 
 def _locations(loc, P):
@@ -96,7 +96,8 @@ class ConvCorrelatedNormal(Prior):
         chol = torch.linalg.cholesky(torch.exp(-d / ls) * scale ** 2)
         W = torch.linalg.inv(chol).T
         lognorm = -0.5 * P * _LOG_2PI - float(torch.log(torch.diagonal(chol)).sum())
-        return dict(P=P, base=0, beta=2.0, base_scale=1.0, lognorm=lognorm, mu=mu, W=W.numpy().copy())
+        return dict(kind=_hip.PRIOR_FILTER_WHITENED, P=P, base=_hip.FILTER_BASE_NORMAL, beta=2.0, base_scale=1.0, lognorm=lognorm,
+                    mu=mu, W=W.numpy().copy())
 
 
 class ConvCorrNormalGamma(ConvCorrelatedNormal):
@@ -179,8 +180,8 @@ class ConvCovariance(Prior):
         if mu is None or base is None:
             return None
         kind, beta, base_scale, base_norm = base
-        return dict(P=P, base=kind, beta=beta, base_scale=base_scale, lognorm=base_norm - P * float(lsv),
-                    mu=mu, W=W.numpy().copy())
+        return dict(kind=_hip.PRIOR_FILTER_WHITENED, P=P, base=kind, beta=beta, base_scale=base_scale,
+                    lognorm=base_norm - P * float(lsv), mu=mu, W=W.numpy().copy())
 
 
 class FixedCovNormal(ConvCovariance):
@@ -191,7 +192,7 @@ class FixedCovNormal(ConvCovariance):
         return td.Normal(zeros, zeros + 1)
 
     def _base_spec(self, P):
-        return 0, 2.0, 1.0, -0.5 * P * _LOG_2PI
+        return _hip.FILTER_BASE_NORMAL, 2.0, 1.0, -0.5 * P * _LOG_2PI
 
 
 class FixedCovLaplace(ConvCovariance):
@@ -209,7 +210,7 @@ class FixedCovLaplace(ConvCovariance):
             return None
         s = float(s)
         # td.Laplace: log p(z) = -log(2 s) - |z| / s
-        return _FILTER_BASE_LAPLACE, 1.0, s, -P * np.log(2.0 * s)
+        return _hip.FILTER_BASE_LAPLACE, 1.0, s, -P * np.log(2.0 * s)
 
 
 class FixedCovDoubleGamma(ConvCovariance):
@@ -237,7 +238,7 @@ class FixedCovDoubleGamma(ConvCovariance):
         c, r = float(c), float(r)
         # DoubleGamma: log p(z) = c log r - lgamma(c) - log 2 + (c - 1) log|z| - r |z|  (prior/distributions.py); the
         # record's beta is c and its base_scale 1 / r
-        return _FILTER_BASE_DOUBLE_GAMMA, c, 1.0 / r, P * (c * np.log(r) - math.lgamma(c) - np.log(2.0))
+        return _hip.FILTER_BASE_DOUBLE_GAMMA, c, 1.0 / r, P * (c * np.log(r) - math.lgamma(c) - np.log(2.0))
 
 
 class FixedCovGenNorm(ConvCovariance):
@@ -260,4 +261,4 @@ class FixedCovGenNorm(ConvCovariance):
             return None
         beta, s = float(beta), float(s)
         # GeneralizedNormal: log p(z) = log beta - log(2 s) - lgamma(1 / beta) - |z / s|^beta  (prior/distributions.py)
-        return 1, beta, s, P * (np.log(beta) - np.log(2.0 * s) - math.lgamma(1.0 / beta))
+        return _hip.FILTER_BASE_GENNORM, beta, s, P * (np.log(beta) - np.log(2.0 * s) - math.lgamma(1.0 / beta))

@@ -18,6 +18,7 @@ from numbers import Number
 import numpy as np
 import torch
 
+from .. import _hip
 from .base import Prior
 from .correlated import _fixed
 from . import distributions
@@ -101,7 +102,7 @@ class MultivariateT(Prior):
         if loc is None or L is None or df is None or df.numel() != 1 or L.dim() != 2 or not self.p.is_contiguous():
             return None
         P = L.shape[-1]
-        if not 1 <= P <= 25 or loc.numel() not in (1, P):            # (SGMCMC_FILTER_MAX_P)
+        if not 1 <= P <= _hip.FILTER_MAX_P or loc.numel() not in (1, P):
             return None
         geo = self.event_geometry()
         D = self.out_event_shape.numel()
@@ -113,5 +114,5 @@ class MultivariateT(Prior):
         lognorm = (math.lgamma((D + df) / 2.0) - math.lgamma(df / 2.0) - (D / 2.0) * math.log(math.pi * lam)
                    - half_log_det)
         W = torch.linalg.inv(L).T
-        return dict(P=P, mu=loc.reshape(-1).expand(P).numpy().copy(), W=W.numpy().copy(), df=df, ev_size=D,
-                    ev_div=int(geo[0]), ev_mod=int(geo[1]), lognorm=lognorm)
+        return dict(kind=_hip.PRIOR_MULTIVARIATE_T, P=P, mu=loc.reshape(-1).expand(P).numpy().copy(), W=W.numpy().copy(),
+                    df=df, ev_size=D, ev_div=int(geo[0]), ev_mod=int(geo[1]), lognorm=lognorm)

@@ -80,10 +80,15 @@ enum {
  * at launch time instead of prior_scale; sgmcmc_prior_grad then also adds
  * -(1/N) (d/dscale sum_j log p(theta_j)) dx/ds to the hyper segment's gradient (flags & SGMCMC_PRIOR_HAS_LINKS).
  *
- * FILTER_WHITENED is not element-wise: a convolution weight [Cout, Cin, kh, kw] in contiguous order is a sequence of
- * filters of P = kh kw consecutive elements, each whitened by the segment's record L->filters[s] (prior/correlated.py):
- *   z = (theta_f - mu) W  (row vector),  log p(theta_f) = sum_k base(z_k) + lognorm,
- *   g_j += -(1/N) sum_k psi(z_k) W[q][k]  with q = j mod P, psi = d base / dz,
+ * FILTER_WHITENED and MULTIVARIATE_T are not element-wise.  A segment of either kind (a convolution weight
+ * [Cout, Cin, kh, kw] in contiguous order, say) is a sequence of filters of P consecutive elements, each whitened by the
+ * segment's record L->filters[s]: z = (theta_f - mu) W (row vector), and element j at position q = j mod P receives
+ *   g_j += -(1/N) coef sum_k psi(z_k) W[q][k],
+ * everything in fp64 with one rounding into g.  Element j reads the other positions of its filter from theta, so both
+ * kinds are evaluated by sgmcmc_prior_grad's full kernel only (a launch that does not write theta); prior_loc /
+ * prior_scale / prior_df are unused.  What each kind adds:
+ *
+ * FILTER_WHITENED (prior/correlated.py): coef = 1, psi = d base / dz, log p(theta_f) = sum_k base(z_k) + lognorm,
  * with the base density chosen by the record's base (SGMCMC_FILTER_BASE_*; their constants are in lognorm):
  *   NORMAL        base(z) = -z^2 / 2                              (beta, base_scale unused)
  *   GENNORM       base(z) = -|z / base_scale|^beta                (beta = shape, base_scale = scale)
@@ -91,15 +96,11 @@ enum {
  *   DOUBLE_GAMMA  base(z) = (beta - 1) log|z| - |z| / base_scale  (beta = concentration c, base_scale = 1 / rate)
  * psi is 0 at z == 0 for every base (where autograd of GENNORM / DOUBLE_GAMMA gives NaN); the DOUBLE_GAMMA log term there
  * follows torch's xlogy: 0 when c == 1, +-inf otherwise.  Any other base value yields NaN (never a silent Normal).
- * Element j reads the other positions of its filter from theta, so it is evaluated by sgmcmc_prior_grad's full
- * kernel only (a launch that does not write theta); prior_loc / prior_scale / prior_df are unused.
  *
- * MULTIVARIATE_T is not per-filter either: the multivariate Student-t of prior/multivariate_t.py (Shah et al.'s
- * parameterisation, lambda = df - 2).  Its record L->filters[s] holds the same P-position whitening (filters of P
- * consecutive elements, z = (theta_f - mu) W) plus an EVENT geometry: element j belongs to event (j / ev_div) % ev_mod,
- * and one event of D = ev_size elements is a whole number of filters.  With M_e = sum over the event's filters of |z|^2,
- *   log p(event) = lognorm - ((df + D) / 2) log(1 + M_e / lambda),
- *   g_j += -(1/N) (-(df + D) / (lambda + M_e)) sum_k z_k W[q][k]  with q = j mod P,
+ * MULTIVARIATE_T (prior/multivariate_t.py; Shah et al.'s parameterisation, lambda = df - 2): psi = z, and the record
+ * also holds an EVENT geometry: element j belongs to event (j / ev_div) % ev_mod, and one event of D = ev_size elements
+ * is a whole number of filters.  With M_e = sum over the event's filters of |z|^2,
+ *   log p(event) = lognorm - ((df + D) / 2) log(1 + M_e / lambda),   coef = -(df + D) / (lambda + M_e),
  * lognorm = lgamma((D + df)/2) - lgamma(df/2) - (D/2) log(pi lambda) - half log |det| of the event.  sgmcmc_prior_grad
  * first writes every event's M_e to the record's ev_sum (one launch, fp64, a fixed summation order: bit-reproducible),
  * then the full kernel applies the gradient; the event's first element (j % ev_div == 0, j < ev_div ev_mod) carries

@@ -1,5 +1,6 @@
 """A plain float64 statement of the element-wise priors of the HIP prior hook (kinds 1-9 of include/sgmcmc_hip.h,
-SURVEY.md Appendix A) with the rounding-error budget of each family next to its formula.
+SURVEY.md Appendix A) with the rounding-error budget of each family next to its formula, and of its two whitened kinds
+(10 and 11: ``whitened``).
 
 Independent of ``bnn_priors_amd.prior``: numpy plus ``math.lgamma`` / ``math.erfc`` / ``math.log1p``.  Inputs are the
 values AS STORED (an fp32 arena's theta, g and raw hyper-parameter s widened exactly); ``loc``, ``scale``, ``df`` and ``N``
@@ -18,6 +19,8 @@ import numpy as np
 NONE, NORMAL, LAPLACE, STUDENT_T, CAUCHY, GENNORM = 0, 1, 2, 3, 4, 5
 GAMMA_SOFTPLUS, UNIFORM_CDF, HALFCAUCHY_SOFTPLUS, IMPROPER_SOFTPLUS = 6, 7, 8, 9
 HYPER_KINDS = (GAMMA_SOFTPLUS, UNIFORM_CDF, HALFCAUCHY_SOFTPLUS, IMPROPER_SOFTPLUS)
+FILTER_WHITENED, MULTIVARIATE_T = 10, 11
+BASE_NORMAL, BASE_GENNORM, BASE_LAPLACE, BASE_DOUBLE_GAMMA = 0, 1, 2, 3
 
 U32, U64 = 2.0 ** -24, 2.0 ** -53
 SAFETY = 2.0
@@ -307,6 +310,46 @@ def check_logp(got, want, bound, what=""):
     err = abs(got - want)
     assert err <= bound, f"{what}: got {got!r}, want {want!r}, |error| {err:.3e} > bound {bound:.3e}"
     return err / bound if bound > 0 else 0.0
+
+
+# --------------------------------------------------------------------------------------------------- whitened kinds
+def whitened(table, theta):
+    """(log p, d log p / d theta, per-event sums or None) of a FILTER_WHITENED or MULTIVARIATE_T table (the dict of
+    ``Prior.fused_filter_spec()`` / ``fused_mvt_spec()``; a table with an event geometry is the multivariate-t one) as
+    include/sgmcmc_hip.h states the two kinds, in float64: z = (theta_f - mu) W per filter of P consecutive elements, then
+
+    FILTER_WHITENED  log p = sum base(z) + lognorm per filter, gradient psi(z) W^T; all four bases, psi = 0 at z == 0 and
+                     the double-Gamma log term as torch's xlogy
+    MULTIVARIATE_T   M_e = sum of |z|^2 over event e's filters, element j in event (j / ev_div) % ev_mod,
+                     log p = sum_e lognorm - (df + D) / 2 log1p(M_e / (df - 2)), gradient -(df + D) / (df - 2 + M_e) z W^T
+
+    The gradient has theta's shape."""
+    n = table["P"]
+    th = np.asarray(theta, dtype=np.float64).reshape(-1, n)
+    W = np.asarray(table["W"], dtype=np.float64)
+    Z = (th - table["mu"]) @ W
+    if "ev_div" in table:
+        ev = (np.arange(th.size) // table["ev_div"]) % table["ev_mod"]
+        M = np.bincount(ev[::n], weights=(Z * Z).sum(1), minlength=table["ev_mod"])
+        lam, c = table["df"] - 2.0, table["df"] + table["ev_size"]
+        lp = float(np.sum(table["lognorm"] - 0.5 * c * np.log1p(M / lam)))
+        g = (-c / (lam + M[ev])) * (Z @ W.T).reshape(-1)
+        return lp, g.reshape(np.shape(theta)), M
+    a, s, beta, kind = np.abs(Z), table.get("base_scale", 1.0), table.get("beta", 2.0), table.get("base", BASE_NORMAL)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        if kind == BASE_NORMAL:
+            base, psi = -0.5 * Z * Z, -Z
+        elif kind == BASE_GENNORM:
+            base, psi = -(a / s) ** beta, -np.sign(Z) * beta / s * (a / s) ** (beta - 1.0)
+        elif kind == BASE_LAPLACE:
+            base, psi = -a / s, -np.sign(Z) / s
+        elif kind == BASE_DOUBLE_GAMMA:
+            base = (0.0 if beta == 1.0 else (beta - 1.0) * np.log(a)) - a / s
+            psi = (beta - 1.0) / Z - np.sign(Z) / s
+        else:
+            raise ValueError(kind)
+    psi = np.where(Z == 0.0, 0.0, psi)
+    return base.sum() + th.shape[0] * table["lognorm"], (psi @ W.T).reshape(np.shape(theta)), None
 
 
 # --------------------------------------------------------------------------------------------------- kernel emulation

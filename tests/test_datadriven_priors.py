@@ -15,6 +15,7 @@ from bnn_priors_amd import _hip
 from bnn_priors_amd import prior as P
 from bnn_priors_amd.prior import loc_scale
 from golden.ref_stubs import REFERENCE_ROOT
+from prior_reference import whitened
 
 DTYPES = (torch.float32, torch.float64)
 
@@ -60,29 +61,6 @@ def _build(z, case, dtype, seed=None):
 
 def _key(case, dtype):
     return f"prior|{case}|{str(dtype)[6:]}|"
-
-
-def kernel_formula(spec, theta):
-    """(log p, d log p / d theta) of the table as the kernel evaluates it (include/sgmcmc_hip.h, FILTER_WHITENED), all
-    four bases, float64; psi = 0 at z == 0 and the double-Gamma log term as torch's xlogy"""
-    n = spec["P"]
-    th = np.asarray(theta, dtype=np.float64).reshape(-1, n)
-    Z = (th - spec["mu"]) @ spec["W"]
-    a, s, beta = np.abs(Z), spec["base_scale"], spec["beta"]
-    with np.errstate(divide="ignore", invalid="ignore"):
-        if spec["base"] == _hip.FILTER_BASE_NORMAL:
-            base, psi = -0.5 * Z * Z, -Z
-        elif spec["base"] == _hip.FILTER_BASE_GENNORM:
-            base, psi = -(a / s) ** beta, -np.sign(Z) * beta / s * (a / s) ** (beta - 1.0)
-        elif spec["base"] == _hip.FILTER_BASE_LAPLACE:
-            base, psi = -a / s, -np.sign(Z) / s
-        elif spec["base"] == _hip.FILTER_BASE_DOUBLE_GAMMA:
-            base = (0.0 if beta == 1.0 else (beta - 1.0) * np.log(a)) - a / s
-            psi = np.where(Z == 0.0, 0.0, (beta - 1.0) / Z - np.sign(Z) / s)
-        else:
-            raise ValueError(spec["base"])
-    psi = np.where(Z == 0.0, 0.0, psi)
-    return base.sum() + th.shape[0] * spec["lognorm"], (psi @ spec["W"].T).reshape(np.shape(theta))
 
 
 def _autograd(pr):
@@ -154,7 +132,7 @@ def test_host_tables_reproduce_the_reference_fixtures(golden_dir, dtype):
         assert pr.fused_spec() is None and pr.fused_mvt_spec() is None
         want_base = _hip.FILTER_BASE_LAPLACE if cfg["cls"] == "FixedCovLaplace" else _hip.FILTER_BASE_DOUBLE_GAMMA
         assert spec["base"] == want_base, case
-        lp, g = kernel_formula(spec, z[key + "theta"])
+        lp, g, _ = whitened(spec, z[key + "theta"])
         tol = _tol(dtype)
         np.testing.assert_allclose(lp, float(z[key + "log_prob"]), **tol, err_msg=case)
         np.testing.assert_allclose(g, z[key + "grad"], rtol=tol["rtol"] * 10, atol=tol["atol"] * 10, err_msg=case)
@@ -203,7 +181,7 @@ def test_kernel_formula_at_the_location():
         spec = pr.fused_filter_spec()
         th = pr.p.detach().numpy().copy()
         th[1, 2] = 0.05                                     # one whole filter at its location
-        lp, g = kernel_formula(spec, th)
+        lp, g, _ = whitened(spec, th)
         assert np.all(np.isfinite(g)) and np.all(g[1, 2] == 0.0), c
         want = {0.5: math.inf, 2.5: -math.inf}.get(c)
         assert lp == want if want is not None else math.isfinite(lp), c
@@ -281,7 +259,7 @@ def test_kernel_matches_the_reference_fixtures(golden_dir, dtype):
         else:
             # float32: the kernel is the float64 formula rounded once into g; the reference's own float32 autograd is
             # further off (large whitening factors of the fitted covariances), so it is held to the host test's tolerance
-            _, formula = kernel_formula(pr.fused_filter_spec(), z[key + "theta"])
+            _, formula, _ = whitened(pr.fused_filter_spec(), z[key + "theta"])
             want = base.double() - torch.from_numpy(formula).to(dev) / N
             torch.testing.assert_close(g.double(), want, rtol=1e-6, atol=1e-6, msg=lambda m: f"{case}: {m}")
             grad = ((base.double() - g.double()) * N).cpu().numpy()
@@ -358,7 +336,7 @@ def test_filters_at_their_location():
             for f in AT_LOCATION:
                 pr.p[f] = 0.02
         spec = pr.fused_filter_spec()
-        want_lp, want_g = kernel_formula(spec, pr.p.detach().numpy())
+        want_lp, want_g, _ = whitened(spec, pr.p.detach().numpy())
         pr = pr.to(dev)
         opt = _fuse([pr], N, chunk=_hip.CHUNK_SMALL)
         g0 = torch.randn(pr.p.shape, dtype=torch.float64, generator=torch.Generator().manual_seed(1)).to(dev)

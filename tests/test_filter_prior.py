@@ -9,25 +9,11 @@ import torch
 
 from bnn_priors_amd import _hip
 from bnn_priors_amd import prior as P
+from prior_reference import whitened
 from test_priors import _build_remaining, _remaining_cases
 
 FILTER_NAMES = ("convcorrnormal", "convcorrnormal_fitted_ls", "fixedcov_normal", "fixedcov_gennorm")
 LEARNABLE_NAMES = ("convcorrnormal_gamma", "convcorrnormal_empirical")
-
-
-def kernel_formula(spec, theta):
-    """(log p, d log p / d theta) of the table as the kernel evaluates it: z = (theta_f - mu) W per filter,
-    log p = sum base(z) + lognorm per filter, gradient psi(z) W^T"""
-    n = spec["P"]
-    th = np.asarray(theta, dtype=np.float64).reshape(-1, n)
-    Z = (th - spec["mu"]) @ spec["W"]
-    if spec["base"] == _hip.FILTER_BASE_GENNORM:
-        a = np.abs(Z) / spec["base_scale"]
-        base = -a ** spec["beta"]
-        psi = -np.sign(Z) * spec["beta"] / spec["base_scale"] * a ** (spec["beta"] - 1.0)
-    else:
-        base, psi = -0.5 * Z * Z, -Z
-    return base.sum() + th.shape[0] * spec["lognorm"], (psi @ spec["W"].T).reshape(np.shape(theta))
 
 
 def _filter_cases(golden_dir, names=FILTER_NAMES):
@@ -43,7 +29,7 @@ def test_host_tables_reproduce_the_reference_fixtures(golden_dir):
         spec = pr.fused_filter_spec()
         assert spec is not None and spec["P"] == 9, key
         assert spec["base"] == (_hip.FILTER_BASE_GENNORM if name == "fixedcov_gennorm" else _hip.FILTER_BASE_NORMAL)
-        lp, g = kernel_formula(spec, pr.p.detach().double().numpy())
+        lp, g, _ = whitened(spec, pr.p.detach().double().numpy())
         tol = dict(rtol=3e-5, atol=3e-5) if dtype == torch.float32 else dict(rtol=1e-10, atol=1e-10)
         np.testing.assert_allclose(lp, float(z[key + "|log_prior"]), **tol, err_msg=key)
         np.testing.assert_allclose(g, z[key + "|grad:p"].reshape(g.shape), rtol=tol["rtol"] * 10, atol=tol["atol"] * 10,
@@ -90,7 +76,7 @@ def test_assign_cov_changes_the_table():
     finally:
         torch.set_default_dtype(torch.float32)
     assert not np.allclose(before["W"], after["W"])
-    lp, g = kernel_formula(after, pr.p.detach().numpy())
+    lp, g, _ = whitened(after, pr.p.detach().numpy())
     want_lp, want_g = _autograd(pr)
     np.testing.assert_allclose(lp, want_lp, rtol=1e-10)
     np.testing.assert_allclose(g, want_g.numpy(), rtol=1e-9, atol=1e-12)

@@ -14,6 +14,7 @@ import torch
 from bnn_priors_amd import _hip
 from bnn_priors_amd import prior as P
 from bnn_priors_amd.prior.distributions import MultivariateT as MVTDist
+from prior_reference import whitened
 
 CASES = ("perm3x3_full", "perm3x3_scalar", "perm1x1", "dense_ed2", "dense_ed1")
 
@@ -40,20 +41,6 @@ def _case(z, name, dtype=torch.float64):
     finally:
         torch.set_default_dtype(torch.float32)
     return pr.to(dtype), cfg
-
-
-def kernel_formula(spec, theta):
-    """(log p, d log p / d theta) of the table as the two launches evaluate it: z = (theta_f - mu) W per filter of P
-    consecutive elements, M_e = sum of |z|^2 over event e's filters, element j in event (j / ev_div) % ev_mod"""
-    th = np.asarray(theta, dtype=np.float64).reshape(-1)
-    n, Pn = th.size, spec["P"]
-    ev = (np.arange(n) // spec["ev_div"]) % spec["ev_mod"]
-    Z = (th.reshape(-1, Pn) - spec["mu"]) @ spec["W"]
-    M = np.bincount(ev[::Pn], weights=(Z * Z).sum(1), minlength=spec["ev_mod"])
-    lam, c = spec["df"] - 2.0, spec["df"] + spec["ev_size"]
-    lp = float(np.sum(spec["lognorm"] - 0.5 * c * np.log1p(M / lam)))
-    g = (-c / (lam + M[ev])) * (Z @ spec["W"].T).reshape(-1)
-    return lp, g.reshape(np.shape(theta))
 
 
 # ---------------------------------------------------------------------------------------------------------------- CPU
@@ -96,7 +83,7 @@ def test_host_table_with_the_kernel_formula_reproduces_the_reference(golden_dir,
     assert spec is not None
     assert spec["P"] == (1 if cfg["factor"] is None else 9)
     assert spec["ev_size"] * spec["ev_mod"] == pr.p.numel()
-    lp, g = kernel_formula(spec, pr.p.detach().numpy())
+    lp, g, _ = whitened(spec, pr.p.detach().numpy())
     assert lp == pytest.approx(float(z["prior|" + name + "|log_prob"]), rel=1e-12)
     np.testing.assert_allclose(g, z["prior|" + name + "|grad"], rtol=1e-10, atol=1e-13)
     assert pr.fused_spec() is None and pr.fused_filter_spec() is None

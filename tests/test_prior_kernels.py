@@ -4,7 +4,8 @@ from the arithmetic the kernel documents instead of an rtol.
 
 CPU: the reference itself against torch.distributions and against the values captured from the original project
 (tests/golden/priors.npz, priors_remaining.npz), and the bounds against numpy emulations of deliberately wrong kernels.
-GPU: tables built from raw specs through ``Engine`` + ``set_priors`` (no Prior module between the test and the kernel).
+GPU: tables built from raw specs through ``Engine`` + ``set_priors`` (no Prior module between the test and the kernel),
+the two whitened kinds (FILTER_WHITENED, MULTIVARIATE_T) included, against ``prior_reference.whitened``.
 
 Every GPU test prints one line ``prior-ratios {...}`` with its worst error / bound per family (docs/lab_notes.md)."""
 import ctypes
@@ -306,8 +307,8 @@ class Arena:
             p.grad = None if i in self.gradless else self.g_buf[o:o + n]
         self.theta0, self.g0 = th, g
 
-    def table(self, specs, links=None):
-        self.engine.set_priors(specs, links)
+    def table(self, specs, links=None, filters=None):
+        self.engine.set_priors(specs, links, filters)
         self.engine.refresh([1.0] * len(self.params), raise_on_no_grad=False)
         assert not self.engine._unaligned
 
@@ -812,3 +813,235 @@ def test_a_nonfinite_parameter_touches_no_other_element(dtype, route):
         assert math.isfinite(per_seg[i]) == math.isfinite(ref["logp"]) and math.isnan(per_seg[i]) == math.isnan(ref["logp"])
         want.append(ref["logp"])
     assert math.isnan(total) == math.isnan(float(np.sum(want))) and not math.isfinite(total)
+
+
+# ===================================================================================================== GPU: whitened kinds
+# kinds 10 and 11 (FILTER_WHITENED, MULTIVARIATE_T) from raw tables against ``R.whitened`` at the stored values, held to
+# the bounds of test_filter_prior.py / test_multivariate_t.py: fp64 gradient rtol 1e-10, atol 1e-12; fp32 gradient one
+# rounding of the result with a safety factor of 2 on top of that allowance; log-priors rel 1e-11, abs 1e-9.
+N_WHITENED = 37.0
+FILTER_P = [1, 3, 9, _hip.FILTER_MAX_P]
+# (name, base, beta, base_scale): GENNORM with beta on both sides of 1 and of 2, DOUBLE_GAMMA with concentration 1 and not 1
+FILTER_BASES = [("normal", R.BASE_NORMAL, 2.0, 1.0), ("gennorm 0.7", R.BASE_GENNORM, 0.7, 0.8),
+                ("gennorm 1.3", R.BASE_GENNORM, 1.3, 0.8), ("gennorm 2.5", R.BASE_GENNORM, 2.5, 1.2),
+                ("laplace", R.BASE_LAPLACE, 1.0, 0.7), ("double-gamma 1", R.BASE_DOUBLE_GAMMA, 1.0, 0.6),
+                ("double-gamma 0.62", R.BASE_DOUBLE_GAMMA, 0.62, 0.9), ("double-gamma 2.5", R.BASE_DOUBLE_GAMMA, 2.5, 0.5)]
+MVT_DF = [2.001, 3.0, 1e4]
+GENNORM_ROW = (R.GENNORM, 0.1, 0.7, 1.7)
+I_W_NONE, I_W_GENNORM = 1, 3            # where the PRIOR_NONE and the element-wise GENNORM segment sit among the whitened ones
+
+
+def _whitening(rng, P):
+    "(mu [P], A [P, P], W = A^-1): theta_f = z A + mu, A = 0.3 (I + E) with |E| about 1/2 (condition number below ~3)"
+    A = 0.3 * (np.eye(P) + 0.25 * rng.standard_normal((P, P)) / math.sqrt(P))
+    return 0.05 * rng.standard_normal(P), A, np.linalg.inv(A)
+
+
+def _filter_table(rng, P, base):
+    _, kind, beta, base_scale = base
+    mu, A, W = _whitening(rng, P)
+    return dict(kind=R.FILTER_WHITENED, P=P, base=kind, beta=beta, base_scale=base_scale, mu=mu, W=W, A=A,
+                lognorm=-0.5 * P * math.log(2.0 * math.pi) - float(np.linalg.slogdet(A)[1]))
+
+
+def _mvt_table(rng, P, df, ev_size, ev_div, ev_mod):
+    mu, A, W = _whitening(rng, P)
+    lognorm = (math.lgamma((ev_size + df) / 2.0) - math.lgamma(df / 2.0) - (ev_size / 2.0) * math.log(math.pi * (df - 2.0))
+               - (ev_size / P) * float(np.linalg.slogdet(A)[1]))
+    return dict(kind=R.MULTIVARIATE_T, P=P, mu=mu, W=W, A=A, df=df, ev_size=ev_size, ev_div=ev_div, ev_mod=ev_mod,
+                lognorm=lognorm)
+
+
+def _filter_sizes(P):
+    """one filter; the largest whole number of filters below a chunk edge and one more (that filter straddles the edge
+    unless P divides it), for both chunk sizes; two large chunks and three filters"""
+    sizes = [P]
+    for edge in (_hip.CHUNK_SMALL, _hip.CHUNK):
+        below = (edge - 1) // P
+        sizes += [below * P, (below + 1) * P]
+    return sizes + [(2 * _hip.CHUNK // P + 3) * P]
+
+
+def _mvt_rows(rng, df):
+    """(numel, table): the whole tensor as one event (700 filters of 3: the lane loop of the event sums takes 11 trips);
+    33 events of 130 one-position filters (a second trip of the event loop, per_run = 130); the permuted convolution
+    geometry [65, 5, 3, 3] (65 filters per event, per_run = 1 with a stride); 45 events of 3 consecutive 25-position filters"""
+    return [(2100, _mvt_table(rng, 3, df, 2100, 2100, 1)), (33 * 130, _mvt_table(rng, 1, df, 130, 130, 33)),
+            (65 * 5 * 9, _mvt_table(rng, 9, df, 65 * 9, 9, 5)), (45 * 75, _mvt_table(rng, 25, df, 75, 75, 45))]
+
+
+def _with_companions(rows, gradless):
+    """the whitened rows [(numel, table)] with a PRIOR_NONE segment, an element-wise GENNORM segment (the ordinary branch of
+    the same launch) and, last, the whitened segment ``gradless`` whose gradient stays None
+    -> (rows [(numel, kind, table)], specs, filters)"""
+    rows = [(n, t["kind"], t) for n, t in list(rows) + [gradless]]
+    rows.insert(I_W_NONE, (11, R.NONE, None))
+    rows.insert(I_W_GENNORM, (7, R.GENNORM, None))
+    specs = [None if k == R.NONE else GENNORM_ROW if k == R.GENNORM else (k, 0.0, 1.0, 0.0) for _, k, _ in rows]
+    return rows, specs, [t for _, _, t in rows]
+
+
+def _whitened_inputs(rng, rows, dtype):
+    "theta = z A + mu with every |z| >= 0.1 (clear of the bases' kink at z == 0; z == 0: test_filters_at_their_location)"
+    thetas = []
+    for n, kind, t in rows:
+        if t is None:
+            thetas.append(_theta(rng, n, GENNORM_ROW[1], kind, dtype, wide=False))
+            continue
+        z = rng.standard_normal((n // t["P"], t["P"]))
+        z = np.sign(z) * (0.1 + np.abs(z))
+        thetas.append((z @ t["A"] + t["mu"]).reshape(-1).astype(_np_dtype(dtype)))
+    return thetas, [_g(rng, n, dtype) for n, _, _ in rows]
+
+
+def _run_whitened(arena, rows, specs, filters, inputs):
+    "-> theta, g, per-segment log-priors, their total, the partials and the event sums after one sgmcmc_prior_grad"
+    arena.load(*inputs)
+    arena.table(specs, filters=filters)
+    flags = arena.engine.prior_flags()
+    assert flags & _hip.PRIOR_FULL and bool(flags & _hip.PRIOR_EVENTS) == any(k == R.MULTIVARIATE_T for _, k, _ in rows)
+    arena.engine.prior_grad(N_WHITENED, True)
+    th, g = arena.read()
+    sums = arena.engine._event_sums
+    return (th, g) + arena.log_priors() + (None if sums is None else sums.cpu().numpy(),)
+
+
+def _hold_whitened(arena, rows, inputs, run, dtype, worst, what, label):
+    "every assertion on one launch; ``label(table)`` names the Worst key of a whitened segment"
+    u = R.unit_roundoff(dtype)
+    th, g, per_seg, total, partials, ev_sum = run
+    thetas, gs = inputs
+    last = len(rows) - 1
+    _check_untouched(arena, th, g, [k for _, k, _ in rows], what)
+    assert per_seg[I_W_NONE] == 0.0
+    assert all(partials[c, 6] == 0.0 for c in arena.chunks_of(last)), what
+    want_total, ev_base = [per_seg[last]], 0
+    for i, (n, kind, t) in enumerate(rows[:last]):
+        case = f"{what} segment {i} ({n} elements)"
+        if kind == R.NONE:
+            continue
+        if kind == R.GENNORM:
+            ref = R.elementwise(kind, *GENNORM_ROW[1:], N_WHITENED, thetas[i], gs[i], u)
+            R.check_gradient(arena.seg(g, i), ref, u, f"element-wise gennorm, {case}")
+            R.check_logp(float(per_seg[i]), ref["logp"], R.logp_bound(ref), f"log-prior of the element-wise gennorm, {case}")
+            want_total.append(ref["logp"])
+            continue
+        lp, grad, M = R.whitened(t, thetas[i].astype(np.float64))
+        want = gs[i].astype(np.float64) - grad / N_WHITENED
+        bound = (2 * u if dtype == "float32" else 0.0) * np.abs(want) + (1e-10 * np.abs(want) + 1e-12)
+        ratio = np.abs(arena.seg(g, i).astype(np.float64) - want) / bound
+        idx = int(np.argmax(ratio))
+        worst.add(label(t), float(ratio[idx]), f"{case} element {idx}")
+        assert ratio[idx] <= 1.0, f"{case} element {idx}: {ratio[idx]:.3f} x bound; {int((ratio > 1).sum())} of {n} outside"
+        lp_bound = 1e-11 * abs(lp) + 1e-9
+        worst.add("log-prior " + label(t), R.check_logp(float(per_seg[i]), lp, lp_bound, f"log-prior, {case}"), case)
+        want_total.append(lp)
+        if M is not None:
+            np.testing.assert_allclose(ev_sum[ev_base:ev_base + M.size], M, rtol=1e-11, atol=0, err_msg=f"event sums, {case}")
+            ev_base += M.size
+    want = math.fsum(want_total)
+    worst.add("log-prior total", R.check_logp(total, want, 1e-11 * abs(want) + 1e-9, f"total log-prior, {what}"), what)
+
+
+def _filter_cases(P, seed):
+    "one table per base: the six sizes of ``_filter_sizes`` and the companions"
+    rng = np.random.default_rng(seed)
+    for base in FILTER_BASES:
+        rows = [(n, _filter_table(rng, P, base)) for n in _filter_sizes(P)]
+        yield base[0], rng, _with_companions(rows, (3 * P, _filter_table(rng, P, base)))
+
+
+def _mvt_cases(seed):
+    rng = np.random.default_rng(seed)
+    for df in MVT_DF:
+        yield f"df {df:g}", rng, _with_companions(_mvt_rows(rng, df), (8 * 6, _mvt_table(rng, 3, df, 6, 6, 8)))
+
+
+def _filter_label(t):
+    return "filter " + next(b[0] for b in FILTER_BASES if b[1:] == (t["base"], t["beta"], t["base_scale"]))
+
+
+@GPU
+@pytest.mark.parametrize("P", FILTER_P)
+@pytest.mark.parametrize("chunk", CHUNKS)
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_whitened_filters_match_the_reference(dtype, chunk, P):
+    """FILTER_WHITENED from raw tables: P = 1, 3, 9 and SGMCMC_FILTER_MAX_P positions, segments that end just below and
+    just beyond the first boundary of either chunk size, every base, next to a PRIOR_NONE, an element-wise GENNORM and a
+    grad-less whitened segment in NaN-padded buffers"""
+    worst = Worst(f"whitened filters {dtype} chunk {chunk} P {P}")
+    arena = None
+    for name, rng, (rows, specs, filters) in _filter_cases(P, 500 + P):
+        arena = arena or Arena([n for n, _, _ in rows], dtype, chunk, gradless=[len(rows) - 1])
+        assert sum(arena.sizes) < 25000
+        inputs = _whitened_inputs(rng, rows, dtype)
+        run = _run_whitened(arena, rows, specs, filters, inputs)
+        assert run[-1] is None
+        _hold_whitened(arena, rows, inputs, run, dtype, worst, f"P {P} base {name}", _filter_label)
+    worst.report()
+
+
+@GPU
+@pytest.mark.parametrize("chunk", CHUNKS)
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_multivariate_t_matches_the_reference(dtype, chunk):
+    """MULTIVARIATE_T from raw tables: the four event geometries of ``_mvt_rows`` at df just above 2, 3 and 1e4 -- the
+    per-event sums, the gradient and the log-priors"""
+    worst = Worst(f"multivariate-t {dtype} chunk {chunk}")
+    arena = None
+    for name, rng, (rows, specs, filters) in _mvt_cases(600):
+        arena = arena or Arena([n for n, _, _ in rows], dtype, chunk, gradless=[len(rows) - 1])
+        assert sum(arena.sizes) < 25000
+        inputs = _whitened_inputs(rng, rows, dtype)
+        run = _run_whitened(arena, rows, specs, filters, inputs)
+        _hold_whitened(arena, rows, inputs, run, dtype, worst, name, lambda t: f"mvt df {t['df']:g}")
+    worst.report()
+
+
+@GPU
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_whitened_bits_do_not_depend_on_the_chunk_size(dtype):
+    """an element's value depends on its index in the segment only, and an event's sum on the segment alone: g of every
+    whitened segment and ev_sum have the same bits at CHUNK and CHUNK_SMALL, and ev_sum again on a second call"""
+    cases = [c for P in FILTER_P for c in _filter_cases(P, 500 + P)] + list(_mvt_cases(600))
+    for name, rng, (rows, specs, filters) in cases:
+        inputs = _whitened_inputs(rng, rows, dtype)
+        runs = []
+        for chunk in CHUNKS:
+            arena = Arena([n for n, _, _ in rows], dtype, chunk, gradless=[len(rows) - 1])
+            runs.append(_run_whitened(arena, rows, specs, filters, inputs))
+            if runs[-1][-1] is not None:
+                again = _run_whitened(arena, rows, specs, filters, inputs)
+                assert_same_bits(again[-1], runs[-1][-1], f"{name}: ev_sum of a second call, chunk {chunk}")
+        for i, (n, kind, t) in enumerate(rows):
+            if t is not None:
+                assert_same_bits(arena.seg(runs[0][1], i), arena.seg(runs[1][1], i), f"{name}: g of segment {i} (P {t['P']})")
+        if runs[0][-1] is not None:
+            assert_same_bits(runs[0][-1], runs[1][-1], f"{name}: ev_sum at the two chunk sizes")
+
+
+@GPU
+def test_prior_grad_refuses_a_filter_table_it_cannot_evaluate():
+    """a layout with a filter table but without SGMCMC_PRIOR_FULL in its prior_flags, and SGMCMC_PRIOR_EVENTS without a
+    filter table: hipErrorInvalidValue, nothing launched"""
+    rng = np.random.default_rng(2)
+    rows, specs, filters = _with_companions([(n, _filter_table(rng, 3, FILTER_BASES[0])) for n in (3, 1026)],
+                                            (9, _filter_table(rng, 3, FILTER_BASES[0])))
+    for case in ("filters without PRIOR_FULL", "PRIOR_EVENTS without filters"):
+        arena = Arena([n for n, _, _ in rows], "float32", _hip.CHUNK_SMALL, gradless=[len(rows) - 1])
+        arena.load(*_whitened_inputs(rng, rows, "float32"))
+        eng = arena.engine
+        if case.startswith("filters"):
+            arena.table(specs, filters=filters)
+            assert eng.layout.filters and eng.layout.prior_flags & _hip.PRIOR_FULL
+            eng.layout.prior_flags = 0
+            flags = _hip.PRIOR_FULL               # (the caller's flags do not stand in for the layout's)
+        else:
+            arena.table([None if s is None else GENNORM_ROW for s in specs])
+            assert not eng.layout.filters
+            flags = _hip.PRIOR_FULL | _hip.PRIOR_EVENTS
+        rc = eng.lib.sgmcmc_prior_grad(ctypes.byref(eng.layout), N_WHITENED, 1, flags, eng.stream())
+        assert rc == INVALID_VALUE, case
+        th, g = arena.read()
+        assert_same_bits(th, arena.theta0, f"{case}: theta")
+        assert_same_bits(g, arena.g0, f"{case}: g")
