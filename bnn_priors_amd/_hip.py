@@ -24,7 +24,7 @@ INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 SOURCES = [os.path.join(_HERE, "csrc", "sgmcmc_hip.hip")]
 SOURCE = SOURCES[0]
 
-ABI_VERSION = 24
+ABI_VERSION = 25
 CHUNK = 4096
 CHUNK_SMALL = 1024
 NSUMS = 6
@@ -191,6 +191,8 @@ GOF_UNIFORM, GOF_NORM, GOF_LAPLACE, GOF_T, GOF_GENNORM, GOF_DGAMMA = 0, 1, 2, 3,
 GOF_DF_RANGE, GOF_BETA_RANGE, GOF_A_RANGE = (0.1, 1e4), (0.1, 10.0), (0.1, 1e4)
 RAOB_MAX_F, RAOB_TILE_ROWS, RAOB_MAX_BLOCKS, RAOB_SCALARS = 64, 64, 256, 16
 TEMPER_SCAN, TEMPER_MAX_LEVELS, TEMPER_UNIFORM_A, TEMPER_UNIFORM_U = 256, 16, 100.0, 0.3
+CORR_TILE, CORR_CHUNK, CORR_MAX_V, CORR_MAX_SPLITS, CORR_TARGET_BLOCKS, CORR_MEAN_BLOCKS = 64, 32, 1024, 64, 1024, 512
+CORR_MAX_BATCH, CORR_STATS = 65535, 5
 
 
 def raob_state_doubles(F):
@@ -203,6 +205,12 @@ class FitGeometry(ctypes.Structure):
     _fields_ = [("P", ctypes.c_int32), ("F", ctypes.c_int32), ("f_major", ctypes.c_int32), ("reserved", ctypes.c_int32),
                 ("events", ctypes.c_int64), ("size", ctypes.c_int64 * 4), ("stride", ctypes.c_int64 * 4),
                 ("f_stride", ctypes.c_int64), ("pos", ctypes.c_int64 * FILTER_MAX_P)]
+
+
+class CorrGeometry(ctypes.Structure):
+    "sgmcmc_corr_geometry"
+    _fields_ = [("V", ctypes.c_int32), ("v_major", ctypes.c_int32), ("n", ctypes.c_int64), ("v_stride", ctypes.c_int64),
+                ("size", ctypes.c_int64 * 4), ("stride", ctypes.c_int64 * 4)]
 
 
 class GofRecord(ctypes.Structure):
@@ -440,6 +448,14 @@ EXPORTS = {
                                               ctypes.c_int64] + [ctypes.c_double] * 3 + [ctypes.c_void_p] * 5),
     "sgmcmc_fit_abs_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(FitGeometry), ctypes.c_double,
                                             ctypes.c_double] + [ctypes.c_void_p] * 5),
+    "sgmcmc_corr_splits": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_int64]),
+    "sgmcmc_corr_mean_blocks": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64]),
+    "sgmcmc_corr_mean": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(CorrGeometry)] + [ctypes.c_void_p] * 5),
+    "sgmcmc_corr_gram": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(CorrGeometry), ctypes.c_int,
+                                        ctypes.c_int64, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    "sgmcmc_corr_finish": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
+                                          ctypes.c_int] + [ctypes.c_void_p] * 5),
+    "sgmcmc_corr_offdiag": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 3),
     "sgmcmc_gof_workspace_doubles": (ctypes.c_int64, [ctypes.c_int64]),
     "sgmcmc_gof_cdf": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(GofRecord),
                                       ctypes.c_void_p, ctypes.c_void_p]),

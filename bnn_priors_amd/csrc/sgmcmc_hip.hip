@@ -1738,6 +1738,9 @@ int sgmcmc_debug_normals(float* out, int64_t start, int64_t n, uint64_t seed, ui
 #include "weights_hip.inc"
 // the data-driven priors fitted to stacks of weight samples: moments, multivariate-t EM, element-wise families (fp64)
 #include "fit_hip.inc"
+// ... and the correlation between the rows, columns or channels of such a stack: means, the centred Gram matrix on the
+// fp64 matrix pipe, cov / corr and the off-diagonal statistics (fp64; after fit_hip.inc: it uses fit::comp_add)
+#include "corr_hip.inc"
 // ... and how well the fitted families describe them: distribution functions in log space, KS / CvM / AD, Q-Q (fp64;
 // after fit_hip.inc as well as summary_hip.inc: it uses fit::comp_add and fit::log_gamma)
 #include "gof_hip.inc"

@@ -186,7 +186,8 @@ def moments(w, P, event_dim=None, permute=None, ddof=1):
     """w [S, *shape] -> ``Moments`` of its n vectors of P positions (``event_dim`` / ``permute`` as ``fit_mvt``; they only
     name which elements form a vector).  The second to fourth moments are centred on a shift taken from the data, so a
     column whose mean is far from 0 keeps its digits.  A NaN or Inf anywhere makes every output NaN.  One pass and one
-    workgroup that adds its partial sums; no host synchronisation."""
+    workgroup that adds its partial sums; no host synchronisation.  For more than 25 positions -- the rows, columns or
+    channels of a layer -- ``weight_correlation.covariance`` forms the covariance and correlation of up to 1,024 variables."""
     g, _, _ = _geometry(w, P, event_dim, permute)
     n = g.events * g.F
     if not isinstance(ddof, int) or not 0 <= ddof < n:

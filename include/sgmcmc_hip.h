@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGMCMC_ABI_VERSION 24
+#define SGMCMC_ABI_VERSION 25
 #define SGMCMC_CHUNK 4096 /* default elements per arena chunk = 256 threads x 4 items x 4 elements */
 #define SGMCMC_CHUNK_SMALL 1024 /* small models: one item per thread, 4x more workgroups */
 #define SGMCMC_NSUMS 6
@@ -1588,6 +1588,74 @@ int sgmcmc_temper_steps(const void* est, int is_f64, int64_t S, int K, int64_t s
                         double* share, double* mean, double* se, int64_t* totals, void* stream);
 int sgmcmc_temper_ewma(const void* x, int is_f64, int R, int64_t S, int64_t stride_r, int64_t stride_s, double alpha,
                        double* y, void* stream);
+
+/* ---- Correlation between the variables of a stack of weight samples (fp64, deterministic) ------------------------------
+ * The second half of the study of trained weights: are the rows, the columns or the channels of a layer correlated, and
+ * compared with what null.  This is the definition, restated in tests/weight_correlation_reference.py.
+ * Stack and geometry.  A stack w [S, *shape] (fp32 or fp64, any strided view) is read in place.  One axis of `shape` holds
+ * the V VARIABLES (variable v at v * v_stride elements); every other axis, S included, indexes the n = S numel(shape) / V
+ * OBSERVATIONS, numbered k = 0 .. n - 1 row-major over the remaining axes in their original order: up to four observation
+ * dimensions (size, stride in elements; unused ones are size 1, neighbours that one stride walks are merged).  v_major != 0
+ * tells the loader that v_stride is below the innermost observation stride, so that a tile is walked variable-first
+ * (coalesced along the stack's fastest dimension); it changes no result.  The Gram entry point takes a leading batch of R
+ * such matrices, matrix r at r * batch_stride elements (R = 1 for a stack; R > 1 for permuted replicates [R][V][n]).
+ * Quantities, all fp64, every operation rounded once:
+ *     m_v = x_v(0) + (sum_k (x_v(k) - x_v(0))) / n   (the mean, summed about the first observation: two passes, so that a
+ *           variable 10^4 standard deviations from 0 keeps its digits and a constant variable has d = 0 exactly)
+ *     d = x - m;   G = d d^T;   cov = G / (n - ddof);   corr_ij = G_ij / sqrt(G_ii G_jj).
+ * A variable with G_vv = 0 is flagged in zero_variance; its cov row and column are 0, its corr row and column NaN, and it
+ * leaves the off-diagonal statistics.  A non-finite element anywhere makes mean, cov and corr NaN (zero_variance 0);
+ * nonfinite[0] counts the elements.
+ * Summation order, a function of (V, n) and of the workspace alone (whatever the strides): observations are cut into
+ * chunks of SGMCMC_CORR_CHUNK.  Mean: workgroup `seg` of sgmcmc_corr_mean_blocks() takes chunks seg, seg + blocks, ...;
+ * slot q = 0 .. 3 of a variable adds observations q, q + 4, ... of a chunk from 0 in ascending order, the chunks' sums are
+ * added in ascending order (compensated, Neumaier), the four slots ((0 + 1) + 2) + 3, the workgroups' partials in
+ * ascending order (compensated).  Gram: G is cut into SGMCMC_CORR_TILE^2 blocks, of which the upper triangle is formed;
+ * workgroup `split` of sgmcmc_corr_splits() takes chunks split, split + splits, ... and accumulates them on the fp64
+ * matrix pipe (v_mfma_f64_16x16x4_f64: four observations per instruction, in the instruction's order, chunk after chunk
+ * in one accumulator); the finish adds the splits from 0 in ascending order and mirrors the triangle.  splits =
+ * min(chunks, SGMCMC_CORR_MAX_SPLITS, SGMCMC_CORR_TARGET_BLOCKS / block pairs, workspace_bytes / (8 V^2)): it does not
+ * depend on R, so a batch gives the bits of R single calls; the slabs take splits * R * V^2 doubles.
+ * Off-diagonal statistics of a correlation matrix [V][V], over the pairs i < j of variables whose diagonal entry is not
+ * NaN (their entries are taken as they are): stats [SGMCMC_CORR_STATS] = {mean r, mean |r|, rms r = sqrt(mean r^2),
+ * max |r|, sum r^2}, all NaN when there is no pair; counts [3] = {pairs, i, j of max |r|: the smallest (i, j) in row-major
+ * order on a tie, (-1, -1) without a pair}.  One workgroup per matrix: thread t adds the pairs (i, i + 1 + t + 256 a),
+ * rows then columns ascending (compensated), then the fixed tree (t += t + 128, ..., t + 1).
+ * No floating-point atomics; two calls give the same bits.  The caller provides every buffer (part: blocks * V doubles,
+ * counts: ceil(V / TILE) * blocks int64); nothing is allocated, nothing synchronises.  Limits: 1 <= V <=
+ * SGMCMC_CORR_MAX_V, 2 <= n < 2^31, 0 <= ddof < n, strides >= 0, the product of the sizes = n, 1 <= R <=
+ * SGMCMC_CORR_MAX_BATCH, 1 <= splits <= min(chunks, SGMCMC_CORR_MAX_SPLITS); anything else or a missing pointer returns
+ * hipErrorInvalidValue and launches nothing. */
+#define SGMCMC_CORR_TILE 64
+#define SGMCMC_CORR_CHUNK 32
+#define SGMCMC_CORR_MAX_V 1024
+#define SGMCMC_CORR_MAX_SPLITS 64
+#define SGMCMC_CORR_TARGET_BLOCKS 1024
+#define SGMCMC_CORR_MEAN_BLOCKS 512
+#define SGMCMC_CORR_MAX_BATCH 65535
+#define SGMCMC_CORR_STATS 5
+typedef struct sgmcmc_corr_geometry {
+  int32_t V, v_major;
+  int64_t n;
+  int64_t v_stride;
+  int64_t size[4], stride[4];
+} sgmcmc_corr_geometry;
+
+/* Workgroups per block pair of the Gram pass (0: workspace_bytes holds no V^2 doubles; -1: a refused shape). */
+int sgmcmc_corr_splits(int V, int64_t n, int64_t workspace_bytes);
+/* Workgroups per variable tile of the mean pass = min(chunks, SGMCMC_CORR_MEAN_BLOCKS / ceil(V / TILE)); -1 if refused. */
+int sgmcmc_corr_mean_blocks(int V, int64_t n);
+/* mean [V], nonfinite [1].  Two launches. */
+int sgmcmc_corr_mean(const void* w, int dtype, const sgmcmc_corr_geometry* geometry, double* part, int64_t* counts,
+                     double* mean, int64_t* nonfinite, void* stream);
+/* slabs [splits][R][V][V], of which the blocks of the upper triangle are written.  mean [V] is shared by the batch. */
+int sgmcmc_corr_gram(const void* x, int dtype, const sgmcmc_corr_geometry* geometry, int R, int64_t batch_stride,
+                     const double* mean, int splits, double* slabs, void* stream);
+/* cov (may be NULL), corr [R][V][V], zero_variance [R][V] (bytes); nonfinite (may be NULL) as sgmcmc_corr_mean wrote it. */
+int sgmcmc_corr_finish(const double* slabs, int splits, int R, int V, int64_t n, int ddof, const int64_t* nonfinite,
+                       double* cov, double* corr, uint8_t* zero_variance, void* stream);
+/* stats [R][SGMCMC_CORR_STATS], counts [R][3] of the R matrices corr [R][V][V]. */
+int sgmcmc_corr_offdiag(const double* corr, int R, int V, double* stats, int64_t* counts, void* stream);
 
 /* Test hook: out[i] = spec normal (fp32) of noise index start+i. */
 int sgmcmc_debug_normals(float* out, int64_t start, int64_t n, uint64_t seed, uint32_t stream,
