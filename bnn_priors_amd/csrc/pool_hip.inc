@@ -101,6 +101,45 @@ extern "C" int sgmcmc_bias_relu_pool_bwd(const float* x, const float* bias, cons
 }
 
 // ------------------------------------------------------------------------------------------------
+// ONE row of the softmax cross-entropy, written once for its three callers: xent::fwd_kernel (a thread per row),
+// head::loss_kernel and lin::fwd_loss_kernel (thread 0 of the row's workgroup).  Same operations in the same order
+// for all of them, so the three routes give the same bits:
+//   m = max_k x_k;  e_k = expf(x_k - m);  s = e_0 + e_1 + ... (in order);  p_k = e_k * (1 / s);
+//   loss = logf(s) - (x_t - m)
+// in : v[0 .. K) the row's logits (K <= KB; the loops have KB steps guarded by k < K, so KB == K folds the guard)
+// out: v[k] = GRAD ? gscale * (p_k - [k == label]) : p_k;  returns the row's loss.
+// The label rule (include/sgmcmc_hip.h, "Labels"): the int64 label is compared as 64 bits against [0, K); a label
+// outside gives a NaN loss and no one-hot term (d = gscale * p), and no address is ever formed from a label -- x_t is
+// selected by comparison, not read at an index.
+namespace xent {
+
+constexpr int kMaxK = 16;
+
+template <int KB, bool GRAD>
+__device__ __forceinline__ float row(float (&v)[KB], int K, int64_t label, float gscale) {
+  float m = -INFINITY;
+#pragma unroll
+  for (int k = 0; k < KB; ++k)
+    if (k < K) m = fmaxf(m, v[k]);
+  float xt = 0.f, s = 0.f;
+#pragma unroll
+  for (int k = 0; k < KB; ++k)
+    if (k < K) {
+      if ((int64_t)k == label) xt = v[k];
+      v[k] = expf(v[k] - m);
+      s += v[k];
+    }
+  const float inv = 1.f / s;
+#pragma unroll
+  for (int k = 0; k < KB; ++k)
+    if (k < K) v[k] = GRAD ? gscale * (v[k] * inv - ((int64_t)k == label ? 1.f : 0.f)) : v[k] * inv;
+  // -log p_t = log s - (x_t - m)
+  return (uint64_t)label < (uint64_t)K ? logf(s) - (xt - m) : __builtin_nanf("");
+}
+
+}  // namespace xent
+
+// ------------------------------------------------------------------------------------------------
 // The classifier head of the ResNet (google_resnet.py:103-110): global average pool over the whole
 // feature map -> Flatten -> Linear, as one operator each way.
 //   forward   pooled[n,c] = mean_p h[n,c,p];  logits[n,k] = b[k] + sum_c W[k,c] pooled[n,c]
@@ -110,7 +149,7 @@ extern "C" int sgmcmc_bias_relu_pool_bwd(const float* x, const float* bias, cons
 // One workgroup per row; C <= 64 channels, P a multiple of 16 with C * 4 <= 256 threads, K <= 16 classes.
 namespace head {
 
-constexpr int kT = 256, kMaxC = 64, kMaxK = 16;
+constexpr int kT = 256, kMaxC = 64, kMaxK = xent::kMaxK;
 
 __global__ __launch_bounds__(kT) void fwd_kernel(const float* __restrict__ h, const float* __restrict__ W,
                                                  const float* __restrict__ b, float* __restrict__ pooled,
@@ -221,7 +260,7 @@ __global__ __launch_bounds__(kT) void loss_kernel(const float* __restrict__ h, c
   // (an unconditional load from an address that is always valid: a value defined inside a branch is waited for at its end)
   const long long cnt = (counting ? counters : reinterpret_cast<const long long*>(y))[counting ? t : 0];
   const float bias_t = (b && t < K) ? b[t] : 0.f;
-  const int tgt_pre = t == 0 ? (int)y[n] : 0;
+  const int64_t tgt_pre = t == 0 ? y[n] : 0;
   constexpr int kPre = 4;
   float4 pre_o[kPre], pre_q[kPre];
   float pre_m[kPre], pre_is[kPre];
@@ -278,21 +317,15 @@ __global__ __launch_bounds__(kT) void loss_kernel(const float* __restrict__ h, c
     logits[(size_t)n * K + t] = a;
   }
   __syncthreads();
-  if (t == 0) {       // the row's softmax cross-entropy, operation by operation as xent::fwd_kernel
-    float v[kMaxK];
-    float m = -INFINITY;
-    for (int k = 0; k < K; ++k) { v[k] = lg[k]; m = fmaxf(m, v[k]); }
-    float sum = 0.f;
-    for (int k = 0; k < K; ++k) { v[k] = expf(v[k] - m); sum += v[k]; }
-    const float inv = 1.f / sum;
-    const int tgt = tgt_pre;
-    const bool valid = (unsigned)tgt < (unsigned)K;      // a label outside [0, K) (e.g. an ignore index): NaN loss row,
-    for (int k = 0; k < K; ++k) {                        // never an out-of-bounds read of the logits
-      const float d = gscale * (v[k] * inv - (k == tgt ? 1.f : 0.f));
-      dl[k] = d;
-      dlogits[(size_t)n * K + k] = d;
-    }
-    loss_rows[n] = valid ? logf(sum) - (lg[tgt] - m) : __builtin_nanf("");
+  if (t == 0) {       // the row's softmax cross-entropy (xent::row: a label outside [0, K), e.g. an ignore index, gives a
+    float v[kMaxK];   // NaN loss row and never an out-of-bounds read of the logits)
+#pragma unroll
+    for (int k = 0; k < kMaxK; ++k)
+      if (k < K) v[k] = lg[k];
+    loss_rows[n] = xent::row<kMaxK, true>(v, K, tgt_pre, gscale);
+#pragma unroll
+    for (int k = 0; k < kMaxK; ++k)
+      if (k < K) { dl[k] = v[k]; dlogits[(size_t)n * K + k] = v[k]; }
   }
   __syncthreads();
   if (t < C) {
@@ -406,8 +439,6 @@ extern "C" int sgmcmc_pool_linear_loss(const float* h, const float* weight, cons
 //   backward: dlogits[b,k] = g * scale * (probs[b,k] - [k == y_b]),  g = *grad_out (a device scalar)
 namespace xent {
 
-constexpr int kMaxK = 16;
-
 // GRAD: instead of the probabilities the kernel leaves d loss / d logits = gscale * (p - onehot) -- exactly what
 // bwd_kernel computes from the saved probabilities with grad_out * scale = gscale -- so a caller that seeds autograd
 // itself (logits.backward(dlogits)) spends one launch on the likelihood instead of three (forward, ones, backward).
@@ -420,21 +451,13 @@ __global__ __launch_bounds__(1024) void fwd_kernel(const float* __restrict__ log
   float l = 0.f;
   if (b < B) {
     float v[kMaxK];
-    float m = -INFINITY;
 #pragma unroll
     for (int k = 0; k < kMaxK; ++k)
-      if (k < K) { v[k] = logits[(size_t)b * K + k]; m = fmaxf(m, v[k]); }
-    float s = 0.f;
+      if (k < K) v[k] = logits[(size_t)b * K + k];
+    l = row<kMaxK, GRAD>(v, K, y[b], gscale);      // (NaN for a label outside [0, K): the total is NaN then)
 #pragma unroll
     for (int k = 0; k < kMaxK; ++k)
-      if (k < K) { v[k] = expf(v[k] - m); s += v[k]; }
-    const float inv = 1.f / s;
-    const int t = (int)y[b];
-#pragma unroll
-    for (int k = 0; k < kMaxK; ++k)
-      if (k < K) probs[(size_t)b * K + k] = GRAD ? gscale * (v[k] * inv - (k == t ? 1.f : 0.f)) : v[k] * inv;
-    // -log p_t = log s - (x_t - m)
-    l = logf(s) - (logits[(size_t)b * K + t] - m);
+      if (k < K) probs[(size_t)b * K + k] = v[k];
   }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) l += __shfl_down(l, off, 64);
@@ -454,7 +477,7 @@ __global__ __launch_bounds__(1024) void bwd_kernel(const float* __restrict__ pro
   if (i >= B * K) return;
   const int b = i / K, k = i % K;
   const float g = grad_out[0] * scale;
-  dlogits[i] = g * (probs[i] - (k == (int)y[b] ? 1.f : 0.f));
+  dlogits[i] = g * (probs[i] - ((int64_t)k == y[b] ? 1.f : 0.f));      // (64-bit compare: the label rule of xent::row)
 }
 
 }  // namespace xent
@@ -558,17 +581,11 @@ __global__ __launch_bounds__(256) void fwd_loss_kernel(const float* __restrict__
   if (threadIdx.x == 0) {
     const int n = blockIdx.x;
     float v[K];
-    float m = -INFINITY;
 #pragma unroll
-    for (int k = 0; k < K; ++k) { v[k] = y[(size_t)n * K + k]; m = fmaxf(m, v[k]); }
-    const int tgt = (int)lab[n];
-    float xt = 0.f, sum = 0.f;
+    for (int k = 0; k < K; ++k) v[k] = y[(size_t)n * K + k];
+    loss_rows[n] = xent::row<K, true>(v, K, lab[n], gscale);
 #pragma unroll
-    for (int k = 0; k < K; ++k) { if (k == tgt) xt = v[k]; v[k] = expf(v[k] - m); sum += v[k]; }
-    const float inv = 1.f / sum;
-#pragma unroll
-    for (int k = 0; k < K; ++k) dlogits[(size_t)n * K + k] = gscale * (v[k] * inv - (k == tgt ? 1.f : 0.f));
-    loss_rows[n] = logf(sum) - (xt - m);
+    for (int k = 0; k < K; ++k) dlogits[(size_t)n * K + k] = v[k];
   }
 }
 

@@ -795,7 +795,8 @@ int sgmcmc_pool_linear_bwd(const float* dlogits, const float* pooled, const floa
  * sgmcmc_pool_linear_fwd, loss_rows[n] = -log softmax(logits_n)[y_n], dlogits = grad_scale * (softmax - onehot) -- the
  * bits of sgmcmc_softmax_xent_fwd_grad -- and dh / slab_w / slab_b (/ partial, with the four bn_* pointers: plane == 64)
  * as sgmcmc_pool_linear_bwd[_sums] would produce from that dlogits.  counters (may be NULL): n_counters <= 256 int64
- * values that get + 1 (the BatchNorm layers' num_batches_tracked, kept in one array).  Replaces the head's Linear,
+ * values that get + 1 (the BatchNorm layers' num_batches_tracked, kept in one array).  A label outside [0, classes):
+ * see "Labels" at sgmcmc_softmax_xent_fwd.  Replaces the head's Linear,
  * Categorical(logits).log_prob and their autograd backward inside R1 (inference.py:215-223, models/base.py:168-191). */
 int sgmcmc_pool_linear_loss(const float* h, const float* weight, const float* bias, const int64_t* y, float* pooled,
                             float* logits, float* dlogits, float* loss_rows, float* dh, float* slab_w, float* slab_b,
@@ -821,7 +822,8 @@ int sgmcmc_linear_fwd(const float* x, const float* weight, const float* bias, fl
                       int out_features, void* stream);
 /* sgmcmc_linear_fwd and, in the same launch, the rows' softmax cross-entropy on the logits it produced: dlogits =
  * grad_scale * (softmax(y_n) - onehot(y_labels[n])) and loss_rows[n] = -log softmax(y_n)[y_labels[n]] -- the bits of
- * sgmcmc_softmax_xent_fwd_grad (models/conv_nets.py:57-70 + models/base.py:168-191 in one launch). */
+ * sgmcmc_softmax_xent_fwd_grad (models/conv_nets.py:57-70 + models/base.py:168-191 in one launch).  A label outside
+ * [0, out_features): see "Labels" at sgmcmc_softmax_xent_fwd. */
 int sgmcmc_linear_fwd_loss(const float* x, const float* weight, const float* bias, const int64_t* y_labels, float* y,
                            float* dlogits, float* loss_rows, int n, int in_features, int out_features,
                            float grad_scale, void* stream);
@@ -877,7 +879,16 @@ int sgmcmc_stage_batch(const void* const* src, void* const* dst, const int64_t* 
 /* loss = scale * sum_b -log softmax(logits_b)[y_b] for up to 1024 rows of up to 16 classes (the likelihood term of
  * models/base.py:168-191), one launch each way: forward keeps probs [rows][classes] for the backward,
  * dlogits = *grad_out * scale * (probs - onehot(y)).  scale = 1/rows for the minibatch mean, 1/N in the exact
- * full-data pass. */
+ * full-data pass.
+ *
+ * Labels -- one rule for every entry point that takes the likelihood: sgmcmc_softmax_xent_fwd / _fwd_grad / _bwd,
+ * sgmcmc_pool_linear_loss and sgmcmc_linear_fwd_loss (one device function, csrc/pool_hip.inc xent::row).  The int64
+ * label is compared as 64 bits against [0, classes): nothing is truncated to 32 bits first.  A label outside that range
+ * (an ignore index, a corrupt batch) gives its row a NaN loss -- so the total of sgmcmc_softmax_xent_fwd[_grad] is NaN --
+ * and a gradient without the one-hot term, dlogits = grad_scale * softmax; every other row is what it would be beside a
+ * valid label.  No address is formed from a label: x_t is selected by comparison, never read at an index, so no label
+ * can make a launch read outside the logits.  (ATen raises a device-side assertion instead, which takes the whole
+ * process's context with it.)  For labels inside the range the three routes give the same bits. */
 int sgmcmc_softmax_xent_fwd(const float* logits, const int64_t* y, float* probs, float* loss, int rows,
                             int classes, double scale, void* stream);
 int sgmcmc_softmax_xent_bwd(const float* probs, const int64_t* y, const float* grad_out, float* dlogits,

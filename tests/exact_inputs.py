@@ -21,6 +21,26 @@ def ints(shape, lo, hi, seed, nonzero=True):
     return (v + (v >= 0).long()).float()
 
 
+GUARD = 256                  # elements behind every guarded output
+
+
+def guarded(shape, dtype=torch.float32, device="cuda"):
+    """a NaN-filled output of ``shape`` with GUARD more NaN elements directly behind it in the same allocation, so that a
+    write past the output's end shows without a fault -> (the output, the whole buffer for ``assert_guard``)"""
+    n = 1
+    for s in shape:
+        n *= s
+    whole = torch.full((n + GUARD,), NAN, dtype=dtype, device=device)
+    return whole[:n].view(tuple(shape)), whole
+
+
+def assert_guard(whole, out, what):
+    "the GUARD elements behind ``out`` still hold the NaN they were filled with"
+    tail = whole[out.numel():]
+    assert tail.numel() == GUARD and bool(torch.isnan(tail).all()), \
+        f"{what}: {int((~torch.isnan(tail)).sum())} of the {GUARD} elements BEHIND the output were written"
+
+
 def assert_budget(*abs_sums):
     """the condition that makes "exact" true: ``abs_sums`` are float64 tensors holding, per output element, the sum of
     the absolute values of its products -- the same operator applied to |x|, |w|, |dy| -- in units of the values' common

@@ -16,7 +16,7 @@ import torch
 import torch.nn.functional as F
 
 from bnn_priors_amd import _hip, conv, pool
-from exact_inputs import NAN, assert_budget, assert_exact, ints
+from exact_inputs import NAN, assert_budget, assert_exact, assert_guard, guarded, ints
 from test_conv import ALT, _check_stats
 
 GPU = pytest.mark.gpu
@@ -62,6 +62,27 @@ N_TAIL = [1, 3, 5, 37, 128]
 POOL_SHAPES = [(128, 50, 28, 28), (37, 50, 14, 14), (5, 3, 6, 10), (1, 1, 2, 2)]
 HEAD_SHAPES = [(64, 8, 10), (16, 4, 3)]
 LINEAR_SHAPES = [(2450, 10), (7, 1), (50, 16)]
+
+# The classifier tail's edge grids (csrc/pool_hip.inc), through the C ABI into guarded outputs.  Crosses, not cubes.
+# lin:: 48 kernels (K = 1..16 x fwd / fwd_loss / bwd); a thread column is 256 wide, one pass of fwd_body / the dx loop
+# 1024 = 256 x CH; the weight gradient walks row groups of 16, and 16 rows x 16 outputs fill the 256-thread staging.
+LIN_J = [1, 255, 256, 257, 1023, 1024, 1025, 2047, 2048, 2049, 2450]
+LIN_N = [1, 15, 16, 17, 31, 32, 33, 128]
+LINEAR_GRID = sorted({(j, k, n, wb) for j, n in ((257, 17), (1025, 16)) for k in range(1, 17) for wb in (True, False)}
+                     | {(j, k, 17, True) for j in LIN_J for k in (1, 10, 16)}
+                     | {(j, k, n, True) for j, k in ((300, 10), (257, 16)) for n in LIN_N})
+# head:: P a power of two (the mean stays exact, each map its own unit 1 / P); C that leave a wave partly active;
+# C * P / 4 below one block stride (256) and off its multiples; P != 64 takes the general pooling loop
+HEAD_C = [1, 3, 16, 33, 63, 64]
+HEAD_MAPS = [(4, 4), (4, 8), (8, 8), (8, 16), (16, 16)]
+HEAD_GRID = [(c, m, k, n) for c, m in sorted({(c, m) for c in HEAD_C for m in ((4, 8), (16, 16))}
+                                             | {(c, m) for c in (3, 64) for m in HEAD_MAPS})
+             for k in (1, 10, 16) for n in (1, 3, 37)]
+# pool::geo, S = 512 / C slices of the batch: S = 1 (C = 512), S clamped from 0 to 1 (C = 513), S recomputed from the
+# images per slice (C = 100, N = 7: 5 -> 4), N < S, W = 2, H != W
+POOL_GRID = [(3, 512, 2, 2), (2, 513, 2, 4), (7, 100, 4, 2), (7, 100, 2, 2), (2, 3, 4, 6), (5, 50, 4, 2), (3, 7, 2, 6), (1, 1, 4, 6)]
+# the head's BatchNorm-backward partials (8 x 8 maps): channels, rows, rows per statistics group (0: one batch)
+SUMS_GRID = [(c, n, g) for c in (1, 16, 33, 64) for n in (1, 3, 6, 37) for g in sorted({0, 1, 3, n}) if g == 0 or n % g == 0]
 
 
 def _trunk_data(c, hw, n):
@@ -140,6 +161,42 @@ def _opt(*ts):
     return tuple(t for t in ts if t is not None)
 
 
+def _head_grid_data(c, m, k, n, with_bias):
+    s = 1000 * c + 100 * m[0] + 10 * m[1] + 7 * k + n
+    return (ints((n, c) + tuple(m), -3, 3, s), ints((k, c), -3, 3, s + 1), ints((k,), -3, 3, s + 2) if with_bias else None,
+            ints((n, k), -3, 3, s + 3))
+
+
+def _sums_data(c, n, group_rows, k=10):
+    """operands of the head's backward with the last BatchNorm's sums: integers, exact zeros under the mask [out > 0],
+    integer BatchNorm input and mean, invstd a power of two per (group,) channel"""
+    s = 77 * c + 5 * n + group_rows
+    groups = n // group_rows if group_rows else 1
+    pick = torch.tensor([0.5, 1.0, 2.0])
+    return dict(dl=ints((n, k), -3, 3, s), pooled=ints((n, c), -3, 3, s + 1), w=ints((k, c), -3, 3, s + 2),
+                y=ints((n, c, 8, 8), -3, 3, s + 3, nonzero=False), out=ints((n, c, 8, 8), -2, 2, s + 4, nonzero=False),
+                mean=ints((groups, c), -2, 2, s + 5, nonzero=False),
+                invstd=pick[ints((groups, c), 0, 2, s + 6, nonzero=False).long()])
+
+
+def _sums_ref(D, group_rows, dev):
+    """float64: dh[n, c, p] = (sum_k dl[n, k] w[k, c]) / 64;  partial[c, n, 0] = sum_p dh [out > 0];
+    partial[c, n, 1] = sum_p dh [out > 0] (y - mean) invstd, with the statistics of the row's group.
+    Budget in units of 1 / 128 (dh is a multiple of 1 / 64, xhat of 1 / 2)."""
+    D = {k: v.to(dev).double() for k, v in D.items()}
+    n, c = D["pooled"].shape
+    g = (torch.arange(n, device=dev) // group_rows) if group_rows else torch.zeros(n, dtype=torch.long, device=dev)
+    dh = ((D["dl"] @ D["w"]) / 64)[:, :, None, None].expand(n, c, 8, 8)
+    a_dh = ((D["dl"].abs() @ D["w"].abs()) / 64)[:, :, None, None].expand(n, c, 8, 8)
+    xhat = (D["y"] - D["mean"][g][:, :, None, None]) * D["invstd"][g][:, :, None, None]
+    mask = (D["out"] > 0).double()
+    assert_budget(128 * (a_dh * mask).sum((2, 3)), 128 * (a_dh * mask * xhat.abs()).sum((2, 3)), 64 * a_dh,
+                  (D["dl"].abs()[:, :, None] * D["pooled"].abs()[:, None, :]).sum(0))
+    partial = torch.stack([(dh * mask).sum((2, 3)).t(), (dh * mask * xhat).sum((2, 3)).t()], dim=-1)       # [c][n][2]
+    slab_w = (D["dl"][:, :, None] * D["pooled"][:, None, :]).reshape(n, -1)
+    return dh.contiguous(), partial.contiguous(), slab_w, D["dl"]
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # 1. the helper and the premise, on the CPU
 
@@ -206,6 +263,29 @@ def test_budget_holds_for_the_other_shapes():
     _ref(_head_op, (h, w, b), (dl,), "cpu", unit=1 / 16)
     x, w, b, dy = _linear_data(2450, 10, 3, True)
     _ref(F.linear, (x, w, b), (dy,), "cpu")
+
+
+def test_budget_holds_for_the_tail_grids():
+    """the classifier tail's edge grids: |values| <= 3, the worst case of each grid in closed form, then the largest cases
+    on inputs as the GPU tests draw them"""
+    for j, k, n, _ in LINEAR_GRID:
+        assert 9 * j + 3 <= 2 ** 24 and 9 * n <= 2 ** 24 and 9 * k <= 2 ** 24          # y, dW / db, dx
+    for c, (h, w), k, n in HEAD_GRID:           # in units of 1 / P: pooled values are sums of P integers, P a power of two
+        P = h * w
+        assert P & (P - 1) == 0 and 9 * P * c + 3 * P <= 2 ** 24 and 9 * P * n <= 2 ** 24 and 9 * k <= 2 ** 24
+    for n, c, h, w in POOL_GRID:
+        assert 3 * n * h * w <= 2 ** 24                                                # the bias gradient
+    for c, n, g in SUMS_GRID:                   # in units of 1 / 128: 64 pixels of |dh| <= 90 / 64 times |xhat| <= 10
+        assert 64 * 128 * (90 / 64) * 10 <= 2 ** 24
+    assert max(j for j, _, _, _ in LINEAR_GRID) == 2450 and max(n for _, _, n, _ in LINEAR_GRID) == 128
+    for j, k, n in ((2450, 16, 17), (300, 10, 128), (1025, 16, 16)):
+        x, w, b, dy = _linear_data(j, k, n, True)
+        _ref(F.linear, (x, w, b), (dy,), "cpu")
+    for c, m, k, n in ((64, (16, 16), 16, 37), (3, (4, 4), 1, 1), (63, (4, 8), 10, 3)):
+        h, w, b, dl = _head_grid_data(c, m, k, n, True)
+        _ref(_head_op, (h, w, b), (dl,), "cpu", unit=1.0 / (m[0] * m[1]))
+    for c, n, g in ((64, 37, 37), (33, 6, 3), (1, 1, 0)):
+        _sums_ref(_sums_data(c, n, g), g, "cpu")
 
 
 @pytest.mark.parametrize("c,hw,n", [(16, 32, 128), (64, 8, 128)])
@@ -691,6 +771,243 @@ def test_narrow_linear(j, k, n, with_bias):
     assert_exact(wg.grad, grads[1], "dW")
     if with_bias:
         assert_exact(bg.grad, grads[2], "db")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 3. the classifier tail at its geometry edges: the C ABI into NaN-filled outputs with a guard tail behind each (a write
+#    at j >= J, past the pass tail of dx or past a slab shows as a touched guard, not as a fault), then through autograd
+
+INVALID = 1          # hipErrorInvalidValue
+
+
+def _p(t):
+    return None if t is None else t.data_ptr()
+
+
+def _stream():
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _check_guards(outs, what):
+    for name, (out, whole) in outs.items():
+        assert_guard(whole, out, f"{what}: {name}")
+
+
+@GPU
+@pytest.mark.parametrize("j,k,n,with_bias", LINEAR_GRID)
+def test_narrow_linear_grid(j, k, n, with_bias):
+    "sgmcmc_linear_fwd / _bwd (every K of the dispatch, J and N on both sides of every stride) and pool.linear"
+    lib = _hip.lib()
+    x, w, b, dy = _linear_data(j, k, n, with_bias)
+    (ry,), grads = _ref(F.linear, _opt(x, w, b), (dy,), "cuda")
+    x, w, b, dy = _cuda(x, w, b, dy)
+    rg = lib.sgmcmc_linear_row_groups(n)
+    assert rg == -(-n // 16)
+    outs = dict(y=guarded((n, k)), dx=guarded((n, j)), slabs=guarded((rg, k, j)), db=guarded((k,)))
+    o = {name: v[0] for name, v in outs.items()}
+    _hip.check(lib.sgmcmc_linear_fwd(x.data_ptr(), w.data_ptr(), _p(b), o["y"].data_ptr(), n, j, k, _stream()), "sgmcmc_linear_fwd")
+    _hip.check(lib.sgmcmc_linear_bwd(x.data_ptr(), w.data_ptr(), dy.data_ptr(), o["dx"].data_ptr(), o["slabs"].data_ptr(),
+                                     o["db"].data_ptr(), n, j, k, _stream()), "sgmcmc_linear_bwd")
+    torch.cuda.synchronize()
+    _check_guards(outs, "narrow linear")
+    assert_exact(o["y"], ry, "y")
+    assert_exact(o["dx"], grads[0], "dx")
+    assert_exact(o["slabs"].double().sum(0), grads[1], "dW (the row groups' slabs, summed)")
+    for g in range(rg):           # ... and every slab is ITS rows' sum
+        rows = slice(16 * g, min(n, 16 * g + 16))
+        assert_exact(o["slabs"][g], dy[rows].double().t() @ x[rows].double(), f"slab of row group {g}")
+    assert_exact(o["db"], dy.double().sum(0), "db")
+    xg, wg, bg = _leaves(x, w, b)
+    y = pool.linear(xg, wg, bg)
+    y.backward(dy)
+    torch.cuda.synchronize()
+    assert_exact(y, ry, "y through autograd")
+    assert_exact(xg.grad, grads[0], "dx through autograd")
+    assert_exact(wg.grad, grads[1], "dW through autograd")
+    if with_bias:
+        assert_exact(bg.grad, grads[2], "db through autograd")
+
+
+@GPU
+@pytest.mark.parametrize("with_bias", [True, False], ids=["bias", "no_bias"])
+@pytest.mark.parametrize("c,m,k,n", HEAD_GRID, ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else str(v))
+def test_pool_linear_head_grid(c, m, k, n, with_bias):
+    "sgmcmc_pool_linear_fwd / _bwd on maps of 16 .. 256 pixels, square or not, and pool.pool_linear"
+    lib, P = _hip.lib(), m[0] * m[1]
+    h, w, b, dl = _head_grid_data(c, m, k, n, with_bias)
+    (ry,), grads = _ref(_head_op, _opt(h, w, b), (dl,), "cuda", unit=1.0 / P)
+    h, w, b, dl = _cuda(h, w, b, dl)
+    outs = dict(pooled=guarded((n, c)), logits=guarded((n, k)), dh=guarded(h.shape), slab_w=guarded((n, k * c)),
+                slab_b=guarded((n, k)))
+    o = {name: v[0] for name, v in outs.items()}
+    _hip.check(lib.sgmcmc_pool_linear_fwd(h.data_ptr(), w.data_ptr(), _p(b), o["pooled"].data_ptr(), o["logits"].data_ptr(),
+                                          n, c, P, k, _stream()), "sgmcmc_pool_linear_fwd")
+    torch.cuda.synchronize()
+    _hip.check(lib.sgmcmc_pool_linear_bwd(dl.data_ptr(), o["pooled"].data_ptr(), w.data_ptr(), o["dh"].data_ptr(),
+                                          o["slab_w"].data_ptr(), o["slab_b"].data_ptr(), n, c, P, k, _stream()),
+               "sgmcmc_pool_linear_bwd")
+    torch.cuda.synchronize()
+    _check_guards(outs, "head")
+    assert_exact(o["pooled"], h.double().mean(dim=(2, 3)), "pooled")
+    assert_exact(o["logits"], ry, "logits")
+    assert_exact(o["dh"], grads[0], "dh")
+    assert_exact(o["slab_w"].double().sum(0).view(k, c), grads[1], "dW (the rows' slabs, summed)")
+    assert_exact(o["slab_b"], dl.double(), "the rows of db")
+    hg, wg, bg = _leaves(h, w, b)
+    out = pool.pool_linear(hg, wg, bg)
+    out.backward(dl)
+    torch.cuda.synchronize()
+    assert_exact(out, ry, "logits through autograd")
+    assert_exact(hg.grad, grads[0], "dh through autograd")
+    assert_exact(wg.grad, grads[1], "dW through autograd")
+    if with_bias:
+        assert_exact(bg.grad, grads[2], "db through autograd")
+
+
+@GPU
+@pytest.mark.parametrize("with_bias", [True, False], ids=["bias", "no_bias"])
+@pytest.mark.parametrize("shape", POOL_GRID)
+def test_bias_relu_pool_grid(shape, with_bias):
+    "the slice geometry of pool::geo at its edges, on tiny planes: integers in [-2, 2] with zeros (ties, x + b == 0)"
+    lib = _hip.lib()
+    n, c, hh, ww = shape
+    s = sum(shape) + with_bias
+    x = ints(shape, -2, 2, s, nonzero=False)
+    b = ints((c,), -1, 1, s + 1, nonzero=False) if with_bias else None
+    dy = ints((n, c, hh // 2, ww // 2), -3, 3, s + 2)
+    op = lambda x, b=None: F.max_pool2d(F.relu(x if b is None else x + b.view(1, -1, 1, 1)), 2)
+    assert_budget(F.interpolate(dy.double().abs(), scale_factor=2, mode="nearest").sum((0, 2, 3)))
+    (ry,), grads = _run64(op, _opt(x, b), (dy,), "cuda")
+    x, b, dy = _cuda(x, b, dy)
+    S = lib.sgmcmc_pool_slices(n, c, hh, ww)
+    want_S = min(max(512 // c, 1), n)
+    want_S = -(-n // -(-n // want_S))
+    assert S == want_S and 1 <= S <= n
+    outs = dict(y=guarded(ry.shape), dx=guarded(shape), part=guarded((S, c)))
+    o = {name: v[0] for name, v in outs.items()}
+    _hip.check(lib.sgmcmc_bias_relu_pool_fwd(x.data_ptr(), _p(b), o["y"].data_ptr(), n, c, hh, ww, _stream()), "sgmcmc_bias_relu_pool_fwd")
+    _hip.check(lib.sgmcmc_bias_relu_pool_bwd(x.data_ptr(), _p(b), dy.data_ptr(), o["dx"].data_ptr(), o["part"].data_ptr(),
+                                             n, c, hh, ww, _stream()), "sgmcmc_bias_relu_pool_bwd")
+    torch.cuda.synchronize()
+    _check_guards(outs, "bias_relu_pool")
+    assert_exact(o["y"], ry, "y")
+    assert_exact(o["dx"], grads[0], "dx")
+    ref_db = grads[1] if with_bias else _run64(op, (x.cpu(), torch.zeros(c)), (dy.cpu(),), "cuda")[1][1]
+    assert_exact(o["part"].double().sum(0), ref_db, "db (the slices' partials, summed)")
+    xg, bg = _leaves(x, b)
+    y = pool.bias_relu_pool(xg, bg)
+    y.backward(dy)
+    torch.cuda.synchronize()
+    assert_exact(y, ry, "y through autograd")
+    assert_exact(xg.grad, grads[0], "dx through autograd")
+    if with_bias:
+        assert_exact(bg.grad, grads[1], "db through autograd")
+
+
+def _sums_outputs(n, c, k):
+    return dict(dh=guarded((n, c, 8, 8)), slab_w=guarded((n, k * c)), slab_b=guarded((n, k)),
+                partial=guarded((c, n, 2), dtype=torch.float64))
+
+
+@GPU
+@pytest.mark.parametrize("c,n,group_rows", SUMS_GRID)
+def test_head_batchnorm_backward_partials(c, n, group_rows):
+    """sgmcmc_pool_linear_bwd_sums: partial[c, n, 0] = sum_p dh [out > 0], partial[c, n, 1] = sum_p dh [out > 0] xhat with
+    the statistics of the row's group, EXACT on integer operands; then sgmcmc_pool_linear_loss with a non-null partial,
+    whose dh / slabs / partials must be, bit for bit, those of the backward kernel fed the loss launch's own dlogits"""
+    lib, k = _hip.lib(), 10
+    D = _sums_data(c, n, group_rows, k)
+    ref_dh, ref_partial, ref_sw, ref_sb = _sums_ref(D, group_rows, "cuda")
+    D = {name: t.cuda() for name, t in D.items()}
+    outs = _sums_outputs(n, c, k)
+    o = {name: v[0] for name, v in outs.items()}
+    _hip.check(lib.sgmcmc_pool_linear_bwd_sums(
+        D["dl"].data_ptr(), D["pooled"].data_ptr(), D["w"].data_ptr(), o["dh"].data_ptr(), o["slab_w"].data_ptr(),
+        o["slab_b"].data_ptr(), D["y"].data_ptr(), D["out"].data_ptr(), D["mean"].data_ptr(), D["invstd"].data_ptr(),
+        o["partial"].data_ptr(), group_rows, n, c, 64, k, _stream()), "sgmcmc_pool_linear_bwd_sums")
+    torch.cuda.synchronize()
+    _check_guards(outs, "bwd_sums")
+    assert_exact(o["dh"], ref_dh, "dh")
+    assert_exact(o["partial"], ref_partial, "BatchNorm-backward partials")
+    assert_exact(o["slab_w"], ref_sw, "the rows of dW")
+    assert_exact(o["slab_b"], ref_sb, "the rows of db")
+    # the fused launch: h = the BatchNorm + ReLU's output (the mask), random valid labels, counters advanced on the way
+    labels = (ints((n,), 0, k - 1, 3 * c + n, nonzero=False)).long().cuda()
+    bias = ints((k,), -3, 3, c + n).cuda()
+    counters = torch.full((21 + 8,), -7, dtype=torch.int64, device="cuda")
+    L = dict(_sums_outputs(n, c, k), pooled=guarded((n, c)), logits=guarded((n, k)), dlogits=guarded((n, k)),
+             loss_rows=guarded((n,)))
+    lo = {name: v[0] for name, v in L.items()}
+    _hip.check(lib.sgmcmc_pool_linear_loss(
+        D["out"].data_ptr(), D["w"].data_ptr(), bias.data_ptr(), labels.data_ptr(), lo["pooled"].data_ptr(),
+        lo["logits"].data_ptr(), lo["dlogits"].data_ptr(), lo["loss_rows"].data_ptr(), lo["dh"].data_ptr(),
+        lo["slab_w"].data_ptr(), lo["slab_b"].data_ptr(), D["y"].data_ptr(), D["out"].data_ptr(), D["mean"].data_ptr(),
+        D["invstd"].data_ptr(), lo["partial"].data_ptr(), group_rows, counters.data_ptr(), 21, n, c, 64, k, 0.25, _stream()),
+        "sgmcmc_pool_linear_loss")
+    torch.cuda.synchronize()
+    _check_guards(L, "pool_linear_loss with sums")
+    assert (counters[:21] == -6).all() and (counters[21:] == -7).all()
+    assert_exact(lo["pooled"], D["out"].double().mean(dim=(2, 3)), "pooled of the fused launch")
+    assert_exact(lo["logits"], F.linear(D["out"].double().mean(dim=(2, 3)), D["w"].double(), bias.double()), "logits of the fused launch")
+    again = _sums_outputs(n, c, k)
+    a = {name: v[0] for name, v in again.items()}
+    _hip.check(lib.sgmcmc_pool_linear_bwd_sums(
+        lo["dlogits"].data_ptr(), lo["pooled"].data_ptr(), D["w"].data_ptr(), a["dh"].data_ptr(), a["slab_w"].data_ptr(),
+        a["slab_b"].data_ptr(), D["y"].data_ptr(), D["out"].data_ptr(), D["mean"].data_ptr(), D["invstd"].data_ptr(),
+        a["partial"].data_ptr(), group_rows, n, c, 64, k, _stream()), "sgmcmc_pool_linear_bwd_sums")
+    torch.cuda.synchronize()
+    for name in ("dh", "slab_w", "slab_b", "partial"):
+        assert torch.equal(lo[name], a[name]), f"{name}: the fused launch and the backward kernel differ"
+    assert not torch.isnan(lo["partial"]).any() and not torch.isnan(lo["loss_rows"]).any()
+
+
+@GPU
+def test_head_entry_points_refuse_what_they_cannot_do():
+    """sums on another plane than 64, a row count that is no multiple of group_rows, 0 or more than 256 counters: each
+    returns hipErrorInvalidValue before any launch -- every output still holds what it was filled with"""
+    lib, n, c, k = _hip.lib(), 6, 16, 10
+    D = {name: t.cuda() for name, t in _sums_data(c, n, 3, k).items()}
+    labels = torch.zeros(n, dtype=torch.int64, device="cuda")
+    counters = torch.full((300,), -7, dtype=torch.int64, device="cuda")
+
+    def bwd_sums(plane, group_rows):
+        outs = _sums_outputs(n, c, k)
+        o = {name: v[0] for name, v in outs.items()}
+        err = lib.sgmcmc_pool_linear_bwd_sums(
+            D["dl"].data_ptr(), D["pooled"].data_ptr(), D["w"].data_ptr(), o["dh"].data_ptr(), o["slab_w"].data_ptr(),
+            o["slab_b"].data_ptr(), D["y"].data_ptr(), D["out"].data_ptr(), D["mean"].data_ptr(), D["invstd"].data_ptr(),
+            o["partial"].data_ptr(), group_rows, n, c, plane, k, _stream())
+        torch.cuda.synchronize()
+        return err, outs
+
+    def loss(plane, group_rows, with_partial, n_counters):
+        outs = dict(_sums_outputs(n, c, k), pooled=guarded((n, c)), logits=guarded((n, k)), dlogits=guarded((n, k)),
+                    loss_rows=guarded((n,)))
+        o = {name: v[0] for name, v in outs.items()}
+        err = lib.sgmcmc_pool_linear_loss(
+            D["out"].data_ptr(), D["w"].data_ptr(), None, labels.data_ptr(), o["pooled"].data_ptr(), o["logits"].data_ptr(),
+            o["dlogits"].data_ptr(), o["loss_rows"].data_ptr(), o["dh"].data_ptr(), o["slab_w"].data_ptr(),
+            o["slab_b"].data_ptr(), D["y"].data_ptr(), D["out"].data_ptr(), D["mean"].data_ptr(), D["invstd"].data_ptr(),
+            o["partial"].data_ptr() if with_partial else None, group_rows,
+            None if n_counters is None else counters.data_ptr(), n_counters or 0, n, c, plane, k, 1.0, _stream())
+        torch.cuda.synchronize()
+        return err, outs
+
+    refused = [("bwd_sums, plane 16", bwd_sums(16, 0)), ("bwd_sums, 6 rows in groups of 4", bwd_sums(64, 4)),
+               ("loss with sums, plane 16", loss(16, 0, True, None)), ("loss, 6 rows in groups of 4", loss(64, 4, True, None)),
+               ("loss, 0 counters", loss(64, 0, True, 0)), ("loss, 257 counters", loss(64, 0, False, 257))]
+    for what, (err, outs) in refused:
+        assert err == INVALID, f"{what}: returned {err}"
+        for name, (out, whole) in outs.items():
+            assert torch.isnan(whole).all(), f"{what}: {name} was written"
+    assert (counters == -7).all()
+    # ... and what they CAN do next to it: the same calls with the offending argument put right
+    for what, (err, outs) in (("bwd_sums", bwd_sums(64, 3)), ("loss", loss(64, 3, True, 256))):
+        assert err == 0, f"{what}: returned {err}"
+        written = [name for name, (out, whole) in outs.items() if not torch.isnan(out).any()]
+        assert "dh" in written and "slab_w" in written, (what, written)
+        _check_guards(outs, what)
+    assert (counters[:256] == -6).all() and (counters[256:] == -7).all()
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -200,16 +200,30 @@ def test_narrow_linear_matches_float64(n, j, k, with_bias):
     assert torch.equal(y2, y)
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("n,reduction,divide_by", [(128, "mean", None), (80, "sum", 50000.0), (3, "mean", None)])
-def test_fused_head_loss_launch_equals_the_three_separate_kernels(n, reduction, divide_by, monkeypatch):
-    """head_loss: logits, loss rows, d loss / d logits and the head's whole backward in ONE launch -- the same bits as
-    pool_linear forward + softmax cross-entropy (fwd + seed) + pool_linear backward, counters advanced on the way"""
+def _same_bits(outs, names):
+    for a, b_, name in zip(outs[0], outs[1], names):
+        if name == "loss":          # the rows are summed by another (ATen) reduction: last-ulp differences
+            torch.testing.assert_close(a, b_, rtol=1e-6, atol=0)
+        else:
+            assert torch.equal(a, b_), name
+
+
+def _loss_rows_match_longdouble(loss_rows, logits, y):
+    """the fused launch's loss rows against longdouble on the logits it produced: within 4 x the deviation of the same
+    operation order restated in float32 (likelihood_reference.py), as in test_likelihood.py"""
+    from likelihood_reference import dev, rows32, rows64
+    lg, lab = logits.detach().cpu().numpy(), y.cpu().numpy()
+    ref, restated = rows64(lg, lab)[0], rows32(lg, lab)[0]
+    got, tol = dev(loss_rows.cpu().numpy(), ref), 4 * dev(restated, ref)
+    assert got <= tol, f"loss rows off by {got:.3e}; 4 x the float32 restatement is {tol:.3e}"
+
+
+def _fused_head_same_bits(n, c, m, k, reduction, divide_by, monkeypatch):
     from bnn_priors_amd import pool
     g = torch.Generator().manual_seed(n)
-    h0 = torch.randn(n, 64, 8, 8, generator=g).cuda()
-    W0, b0 = (torch.randn(10, 64, generator=g) * 0.2).cuda(), torch.randn(10, generator=g).cuda()
-    y = torch.randint(0, 10, (n,), generator=g).cuda()
+    h0 = torch.randn(n, c, m[0], m[1], generator=g).cuda()
+    W0, b0 = (torch.randn(k, c, generator=g) * 0.2).cuda(), torch.randn(k, generator=g).cuda()
+    y = torch.randint(0, k, (n,), generator=g).cuda()
     outs = []
     for fused in (False, True):
         monkeypatch.setattr(pool, "FUSED_HEAD", fused)
@@ -217,15 +231,62 @@ def test_fused_head_loss_launch_equals_the_three_separate_kernels(n, reduction, 
         counters = torch.arange(21, dtype=torch.int64).cuda()
         with pool.head_loss(y, reduction, divide_by):
             f = pool.pool_linear(h, W, b, counters)
+        f.retain_grad()
         assert hasattr(f, "_sgmcmc_head_loss") == fused
+        if fused:
+            _loss_rows_match_longdouble(f._sgmcmc_head_loss[2], f, y)
         loss = pool.cross_entropy_backward(f, y, reduction, divide_by)
         assert torch.equal(counters.cpu(), torch.arange(21) + 1)
-        outs.append((f.detach(), loss.detach(), h.grad, W.grad, b.grad))
-    for a, b_, name in zip(outs[0], outs[1], ("logits", "loss", "dh", "dW", "db")):
-        if name == "loss":          # the rows are summed by another (ATen) reduction: last-ulp differences
-            torch.testing.assert_close(a, b_, rtol=1e-6, atol=0)
-        else:
-            assert torch.equal(a, b_), name
+        outs.append((f.detach(), loss.detach(), f.grad, h.grad, W.grad, b.grad))
+    _same_bits(outs, ("logits", "loss", "d", "dh", "dW", "db"))
+    return h0, W0, y
+
+
+def _fused_linear_same_bits(n, j, k, reduction, divide_by, monkeypatch):
+    from bnn_priors_amd import pool
+    g = torch.Generator().manual_seed(n)
+    x0 = torch.randn(n, j, generator=g).cuda()
+    W0, b0 = (torch.randn(k, j, generator=g) * 0.02).cuda(), torch.randn(k, generator=g).cuda()
+    y = torch.randint(0, k, (n,), generator=g).cuda()
+    outs = []
+    for fused in (False, True):
+        monkeypatch.setattr(pool, "FUSED_HEAD", fused)
+        x, W, b = x0.clone().requires_grad_(), W0.clone().requires_grad_(), b0.clone().requires_grad_()
+        with pool.head_loss(y, reduction, divide_by):
+            f = pool.linear(x, W, b)
+        f.retain_grad()
+        assert hasattr(f, "_sgmcmc_head_loss") == fused
+        if fused:
+            _loss_rows_match_longdouble(f._sgmcmc_head_loss[2], f, y)
+        loss = pool.cross_entropy_backward(f, y, reduction, divide_by)
+        outs.append((f.detach(), loss.detach(), f.grad, x.grad, W.grad, b.grad))
+    _same_bits(outs, ("logits", "loss", "d", "dx", "dW", "db"))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("c,m,k,n", [(64, (8, 8), 10, 128), (3, (4, 8), 1, 3), (33, (16, 16), 16, 5), (63, (4, 4), 7, 65)],
+                         ids=["64x8x8-K10-N128", "3x4x8-K1-N3", "33x16x16-K16-N5", "63x4x4-K7-N65"])
+@pytest.mark.parametrize("reduction,divide_by", [("mean", None), ("sum", 50000.0)])
+def test_fused_head_loss_launch_has_the_separate_kernels_bits_at_the_edges(c, m, k, n, reduction, divide_by, monkeypatch):
+    "the general pooling loop (P != 64), a non-square map, K = 1 and 16, channel counts that leave a wave partly active"
+    _fused_head_same_bits(n, c, m, k, reduction, divide_by, monkeypatch)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("j,k,n", [(2450, 10, 128), (257, 1, 17), (1025, 16, 33)])
+@pytest.mark.parametrize("reduction,divide_by", [("mean", None), ("sum", 60000.0)])
+def test_fused_linear_forward_and_loss_has_the_two_kernels_bits_at_the_edges(j, k, n, reduction, divide_by, monkeypatch):
+    "K = 1 and 16, J one past a thread column and one past a pass, N one past a row group"
+    _fused_linear_same_bits(n, j, k, reduction, divide_by, monkeypatch)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n,reduction,divide_by", [(128, "mean", None), (80, "sum", 50000.0), (3, "mean", None)])
+def test_fused_head_loss_launch_equals_the_three_separate_kernels(n, reduction, divide_by, monkeypatch):
+    """head_loss: logits, loss rows, d loss / d logits and the head's whole backward in ONE launch -- the same bits as
+    pool_linear forward + softmax cross-entropy (fwd + seed) + pool_linear backward, counters advanced on the way"""
+    from bnn_priors_amd import pool
+    h0, W0, y = _fused_head_same_bits(n, 64, (8, 8), 10, reduction, divide_by, monkeypatch)
     # other labels / another reduction than announced: the tagged logits are not used
     monkeypatch.setattr(pool, "FUSED_HEAD", True)
     h, W = h0.clone().requires_grad_(), W0.clone().requires_grad_()
@@ -243,25 +304,7 @@ def test_fused_head_loss_launch_equals_the_three_separate_kernels(n, reduction, 
 @pytest.mark.parametrize("n,reduction,divide_by", [(128, "mean", None), (96, "sum", 60000.0)])
 def test_fused_linear_forward_and_loss_equals_the_two_kernels(n, reduction, divide_by, monkeypatch):
     "the convolutional classifier's head: linear forward + softmax cross-entropy seed in one launch, same bits"
-    from bnn_priors_amd import pool
-    g = torch.Generator().manual_seed(n)
-    x0 = torch.randn(n, 2450, generator=g).cuda()
-    W0, b0 = (torch.randn(10, 2450, generator=g) * 0.02).cuda(), torch.randn(10, generator=g).cuda()
-    y = torch.randint(0, 10, (n,), generator=g).cuda()
-    outs = []
-    for fused in (False, True):
-        monkeypatch.setattr(pool, "FUSED_HEAD", fused)
-        x, W, b = x0.clone().requires_grad_(), W0.clone().requires_grad_(), b0.clone().requires_grad_()
-        with pool.head_loss(y, reduction, divide_by):
-            f = pool.linear(x, W, b)
-        assert hasattr(f, "_sgmcmc_head_loss") == fused
-        loss = pool.cross_entropy_backward(f, y, reduction, divide_by)
-        outs.append((f.detach(), loss.detach(), x.grad, W.grad, b.grad))
-    for a, b_, name in zip(outs[0], outs[1], ("logits", "loss", "dx", "dW", "db")):
-        if name == "loss":
-            torch.testing.assert_close(a, b_, rtol=1e-6, atol=0)
-        else:
-            assert torch.equal(a, b_), name
+    _fused_linear_same_bits(n, 2450, 10, reduction, divide_by, monkeypatch)
 
 
 @pytest.mark.gpu
