@@ -23,74 +23,6 @@ constexpr int kMaxRows = 131072;
 constexpr int kMaxBins = 4096;
 constexpr double kEps = 2.220446049250313e-16;   // np.finfo(np.float64).eps = 2^-52
 
-// max-prob, first index of the maximum (np.argmax: a NaN wins and the first NaN is kept) and hit of one row
-__device__ __forceinline__ void row_max(const double* p, int C, int64_t n, const int64_t* __restrict__ labels,
-                                        double* __restrict__ conf, int64_t* __restrict__ pred,
-                                        int64_t* __restrict__ hit) {
-  double best = p[0];
-  int arg = 0;
-  for (int c = 1; c < C; ++c) {
-    const double v = p[c];
-    if (v > best || (v != v && best == best)) { best = v; arg = c; }
-  }
-  conf[n] = best;
-  pred[n] = arg;
-  if (hit) hit[n] = (labels[n] == (int64_t)arg) ? 1 : 0;
-}
-
-// one term of a running sum_e exp(x_e - m): a NaN survives an all -inf column
-__device__ __forceinline__ double lse_term(double x, double m) {
-  return m == -INFINITY ? (x != x ? x : 0.0) : exp(x - m);
-}
-
-// The running log-sum-exp over the samples of one (row, class) entry, (m, s) with sum_e exp(x_e) = s exp(m): four
-// samples at a time, then one at a time, then the log-mean.  ensemble_kernel and uncert::rows_kernel (uncert_hip.inc)
-// both run exactly this sequence, which is what makes their probabilities the same bits.
-// (f: the factor s took when the maximum moved, 1 otherwise; t[i]: the term exp(x_i - m) that was added -- for a caller
-// that carries a second sum on the same maximum)
-__device__ __forceinline__ void lse_add4(double& m, double& s, double x0, double x1, double x2, double x3, double& f,
-                                         double* t) {
-  const double mx = fmax(fmax(m, fmax(x0, x1)), fmax(x2, x3));
-  f = 1.0;
-  if (mx > m) {
-    if (m != -INFINITY) { f = exp(m - mx); s = s * f; }
-    m = mx;
-  }
-  t[0] = lse_term(x0, m); t[1] = lse_term(x1, m); t[2] = lse_term(x2, m); t[3] = lse_term(x3, m);
-  s = (((s + t[0]) + t[1]) + t[2]) + t[3];
-}
-
-__device__ __forceinline__ void lse_add1(double& m, double& s, double x, double& f, double& t) {
-  f = 1.0;
-  if (x > m) {
-    if (m != -INFINITY) { f = exp(m - x); s = s * f; }
-    m = x;
-  }
-  t = lse_term(x, m);
-  s += t;
-}
-
-__device__ __forceinline__ void lse_add4(double& m, double& s, double x0, double x1, double x2, double x3) {
-  double f, t[4];
-  lse_add4(m, s, x0, x1, x2, x3, f, t);
-}
-
-__device__ __forceinline__ void lse_add1(double& m, double& s, double x) {
-  double f, t;
-  lse_add1(m, s, x, f, t);
-}
-
-__device__ __forceinline__ double lse_log_mean(double m, double s, int E) { return (m + log(s)) - log((double)E); }
-
-// softmax of the C log-means in l (LDS), in place and to p (global): the ensemble's probabilities of one row
-__device__ __forceinline__ void row_softmax(double* l, int C, double* __restrict__ p) {
-  double mx = l[0];
-  for (int k = 1; k < C; ++k) mx = fmax(mx, l[k]);
-  double s = 0.0;
-  for (int k = 0; k < C; ++k) { l[k] = exp(l[k] - mx); s += l[k]; }
-  for (int k = 0; k < C; ++k) { l[k] = l[k] / s; p[k] = l[k]; }
-}
-
 __global__ __launch_bounds__(256) void ensemble_kernel(const double* __restrict__ acc, const int64_t* __restrict__ labels,
                                                        int E, int N, int C, double* __restrict__ probs,
                                                        double* __restrict__ conf, int64_t* __restrict__ pred,
@@ -105,17 +37,17 @@ __global__ __launch_bounds__(256) void ensemble_kernel(const double* __restrict_
     double m = -INFINITY, s = 0.0;
     int e = 0;
     for (; e + 4 <= E; e += 4)
-      lse_add4(m, s, a[(size_t)e * plane], a[(size_t)(e + 1) * plane], a[(size_t)(e + 2) * plane],
-               a[(size_t)(e + 3) * plane]);
-    for (; e < E; ++e) lse_add1(m, s, a[(size_t)e * plane]);
-    row[t] = lse_log_mean(m, s, E);
+      num::lse_add4(m, s, a[(size_t)e * plane], a[(size_t)(e + 1) * plane], a[(size_t)(e + 2) * plane],
+                    a[(size_t)(e + 3) * plane]);
+    for (; e < E; ++e) num::lse_add1(m, s, a[(size_t)e * plane]);
+    row[t] = num::lse_log_mean(m, s, E);
   }
   __syncthreads();
   const int64_t n = n0 + t;
   if (t < rows && n < N) {
     double* l = row + t * C;
-    row_softmax(l, C, probs + n * C);
-    row_max(l, C, n, labels, conf, pred, hit);
+    num::row_softmax(l, C, probs + n * C);
+    num::row_max(l, C, n, labels, conf, pred, hit);
   }
 }
 
@@ -123,7 +55,7 @@ __global__ __launch_bounds__(256) void row_max_kernel(const double* __restrict__
                                                       int N, int C, double* __restrict__ conf,
                                                       int64_t* __restrict__ pred, int64_t* __restrict__ hit) {
   const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (n < N) row_max(probs + n * C, C, n, labels, conf, pred, hit);
+  if (n < N) num::row_max(probs + n * C, C, n, labels, conf, pred, hit);
 }
 
 // fp64 -> uint64 with the same order as numpy's sort: -0.0 and 0.0 equal, NaN (any payload) last
@@ -261,21 +193,6 @@ __global__ void calib_combine_kernel(const double* __restrict__ col_err, int nco
 constexpr int kRankThreads = 1024;
 constexpr int kNone = 0x7fffffff;
 
-// Hillis-Steele scan over one value per thread (buf holds the inputs and ends holding the scan): inclusive prefix
-// sums, or inclusive suffix minima
-template <bool kSuffixMin>
-__device__ __forceinline__ void block_scan(int* buf) {
-  const int t = threadIdx.x;
-  for (int off = 1; off < kRankThreads; off <<= 1) {
-    int v;
-    if (kSuffixMin) v = t + off < kRankThreads ? buf[t + off] : kNone;
-    else v = t >= off ? buf[t - off] : 0;
-    __syncthreads();
-    buf[t] = kSuffixMin ? min(buf[t], v) : buf[t] + v;
-    __syncthreads();
-  }
-}
-
 // rows [0, n_pos) of scores are the positives (in-distribution), [n_pos, n) the negatives; perm: their ascending
 // stable order.  out[0] = AUROC, out[1] = average precision, out[2] = 1 if a score is NaN (then out[0..1] = NaN)
 __global__ __launch_bounds__(kRankThreads) void rank_kernel(const double* __restrict__ scores,
@@ -304,8 +221,8 @@ __global__ __launch_bounds__(kRankThreads) void rank_kernel(const double* __rest
   before[t] = pb;
   sfx[t] = fs;
   __syncthreads();
-  block_scan<false>(incl);                        // incl[t] = #positives at positions < q1
-  block_scan<true>(sfx);                          // sfx[t] = the first group start in chunks >= t
+  num::block_scan<int, num::Add, false, kRankThreads>(incl, num::Add());     // incl[t] = #positives at positions < q1
+  num::block_scan<int, num::Min, true, kRankThreads>(sfx, num::Min());      // sfx[t] = the first group start in chunks >= t
   const int nxt = t + 1 < kRankThreads ? sfx[t + 1] : kNone;
   // walk the chunk downwards: a group [q, e) with e the next start above it.  prefix(x) = #positives below x,
   // tp(x) = P - prefix(x), fp(x) = (n - x) - tp(x): the cumulative counts at the threshold sorted(x), from the top

@@ -1,6 +1,6 @@
 // Weight-correlation analysis (include/sgmcmc_hip.h, "Correlation between the variables of a stack"): per-variable means,
 // the centred Gram matrix G = d d^T on the fp64 matrix pipe, cov / corr and the off-diagonal statistics of a correlation
-// matrix.  Included from sgmcmc_hip.hip after fit_hip.inc (it uses fit::comp_add and fit::qnan).
+// matrix.  Included from sgmcmc_hip.hip after numerics_hip.inc (it uses num::comp_add and num::qnan).
 //
 // One loader serves the mean and the Gram pass: a tile of kTile variables x kChunk observations is read through the
 // strided geometry with consecutive lanes on consecutive addresses -- along the variables when the variable stride is the
@@ -151,7 +151,7 @@ __global__ __launch_bounds__(kThreads) void mean_kernel(const T* __restrict__ x,
     double ts = 0.0;
 #pragma unroll
     for (int k = 0; k < kChunk; k += 4) ts += row[k];
-    fit::comp_add(acc, comp, ts);                       // ... and the chunks' sums in ascending order, compensated
+    num::comp_add(acc, comp, ts);                       // ... and the chunks' sums in ascending order, compensated
   }
   sSum[t] = acc + comp;
   if (bad) atomicAdd(&sBad, bad);                       // (an integer in LDS: exact in any order)
@@ -172,8 +172,8 @@ __global__ __launch_bounds__(kThreads) void mean_finish_kernel(const T* __restri
   if (v == 0) nonfinite[0] = bad;
   if (v >= g.V) return;
   double s = 0.0, c = 0.0;
-  for (int q = 0; q < segs; ++q) fit::comp_add(s, c, part[(size_t)q * g.V + v]);
-  mean[v] = bad ? fit::qnan() : (double)x[(int64_t)v * g.v_stride] + (s + c) / (double)g.n;
+  for (int q = 0; q < segs; ++q) num::comp_add(s, c, part[(size_t)q * g.V + v]);
+  mean[v] = bad ? num::qnan() : (double)x[(int64_t)v * g.v_stride] + (s + c) / (double)g.n;
 }
 
 // ---- 2. Gram pass: slab[split][r] block (bi, bj), bi <= bj, = sum over the chunks split, split + splits, ... of d d^T --
@@ -263,8 +263,8 @@ __global__ __launch_bounds__(kThreads) void finish_kernel(const double* __restri
   }
   const bool bad = nonfinite && nonfinite[0] != 0, flat = gaa == 0.0 || gbb == 0.0;
   const size_t o = (size_t)rep * V * V + idx;
-  if (cov) cov[o] = bad ? fit::qnan() : flat ? 0.0 : gab / denom;
-  corr[o] = bad || flat ? fit::qnan() : gab / sqrt(gaa * gbb);
+  if (cov) cov[o] = bad ? num::qnan() : flat ? 0.0 : gab / denom;
+  corr[o] = bad || flat ? num::qnan() : gab / sqrt(gaa * gbb);
   if (i == j) zero_variance[(size_t)rep * V + i] = !bad && gaa == 0.0;
 }
 
@@ -294,9 +294,9 @@ __global__ __launch_bounds__(kThreads) void offdiag_kernel(const double* __restr
     for (int j = i + 1 + t; j < V; j += kThreads) {
       if (!sIn[j]) continue;
       const double r = corr[(size_t)i * V + j], ar = fabs(r);
-      fit::comp_add(s[0], c[0], r);
-      fit::comp_add(s[1], c[1], ar);
-      fit::comp_add(s[2], c[2], r * r);
+      num::comp_add(s[0], c[0], r);
+      num::comp_add(s[1], c[1], ar);
+      num::comp_add(s[2], c[2], r * r);
       ++cnt;
       if (mi < 0 || ar > m) m = ar, mi = i, mj = j;     // (rows and columns ascend: the first of a tie stays)
     }
@@ -318,11 +318,11 @@ __global__ __launch_bounds__(kThreads) void offdiag_kernel(const double* __restr
     double* out = stats + (size_t)blockIdx.x * kStats;
     long long* cn = counts + (size_t)blockIdx.x * 3;
     const bool none = sN[0] == 0;
-    out[0] = none ? fit::qnan() : sS[0][0] / np;
-    out[1] = none ? fit::qnan() : sS[1][0] / np;
-    out[2] = none ? fit::qnan() : sqrt(sS[2][0] / np);
-    out[3] = none ? fit::qnan() : sM[0];
-    out[4] = none ? fit::qnan() : sS[2][0];
+    out[0] = none ? num::qnan() : sS[0][0] / np;
+    out[1] = none ? num::qnan() : sS[1][0] / np;
+    out[2] = none ? num::qnan() : sqrt(sS[2][0] / np);
+    out[3] = none ? num::qnan() : sM[0];
+    out[4] = none ? num::qnan() : sS[2][0];
     cn[0] = sN[0], cn[1] = sI[0], cn[2] = sJ[0];
   }
 }

@@ -44,14 +44,8 @@ inline int blocks(int P, int F, int64_t events) {
   return (int)(tiles < kMaxBlocks ? tiles : kMaxBlocks);
 }
 
-__device__ __forceinline__ double qnan() { return __longlong_as_double(0x7ff8000000000000ll); }
-
-// s + c += v (Neumaier), as uncert::comp_add: the sums over tiles and over workgroups
-__device__ __forceinline__ void comp_add(double& s, double& c, double v) {
-  const double t = s + v;
-  c += fabs(s) >= fabs(v) ? (s - t) + v : (v - t) + s;
-  s = t;
-}
+using num::comp_add;
+using num::qnan;
 
 // element offset of event e (< 2^31): its index is decomposed over the event dimensions, outermost first
 __device__ __forceinline__ int64_t event_offset(const Geom& g, uint32_t e) {
@@ -66,36 +60,6 @@ __device__ __forceinline__ int64_t event_offset(const Geom& g, uint32_t e) {
     }
   }
   return off;
-}
-
-// digamma and trigamma for x > 0: the recurrence up to x >= 10, then the asymptotic series through B_14 (the first
-// term left out is below 5e-17 there)
-__device__ __forceinline__ double digamma(double x) {
-  double r = 0.0;
-  while (x < 10.0) { r -= 1.0 / x; x += 1.0; }
-  const double f = 1.0 / (x * x);
-  const double t = f * (1.0 / 12 - f * (1.0 / 120 - f * (1.0 / 252 - f * (1.0 / 240 - f * (1.0 / 132
-                   - f * (691.0 / 32760 - f * (1.0 / 12)))))));
-  return r + (log(x) - 0.5 / x - t);
-}
-__device__ __forceinline__ double trigamma(double x) {
-  double r = 0.0;
-  while (x < 10.0) { r += 1.0 / (x * x); x += 1.0; }
-  const double f = 1.0 / (x * x);
-  const double t = (f / x) * (1.0 / 6 - f * (1.0 / 30 - f * (1.0 / 42 - f * (1.0 / 30 - f * (5.0 / 66
-                   - f * (691.0 / 2730 - f * (7.0 / 6)))))));
-  return r + (1.0 / x + 0.5 * f + t);
-}
-
-// log Gamma(x) for x > 0: lgamma(x) = lgamma(x + k) - log(x (x + 1) .. (x + k - 1)) up to x + k >= 10, then Stirling's
-// series through B_14
-__device__ __forceinline__ double log_gamma(double x) {
-  double prod = 1.0;
-  while (x < 10.0) { prod *= x; x += 1.0; }
-  const double f = 1.0 / (x * x);
-  const double t = (1.0 / x) * (1.0 / 12 - f * (1.0 / 360 - f * (1.0 / 1260 - f * (1.0 / 1680 - f * (1.0 / 1188
-                   - f * (691.0 / 360360 - f * (1.0 / 156)))))));
-  return (((x - 0.5) * log(x) - x) + 0.91893853320467274178 + t) - log(prod);
 }
 
 // entry `ent` of a partial record -> what it sums: 0 w d_a d_b, 1 w d_a, 2 d_a^3, 3 d_a^4, 4 sum u, 5 sum (log u - u),
@@ -421,14 +385,14 @@ __global__ __launch_bounds__(64) void mvt_init_kernel(int P, const double* __res
 // the root in [lo, hi] of g(nu) = log(nu / 2) - psi(nu / 2) + c (decreasing): Newton from nu0, bisection when a step
 // leaves the bracket
 __device__ __forceinline__ double solve_nu(double c, double nu0, double lo, double hi) {
-  auto g = [c](double nu) { return (log(0.5 * nu) - digamma(0.5 * nu)) + c; };
+  auto g = [c](double nu) { return (log(0.5 * nu) - num::digamma(0.5 * nu)) + c; };
   if (!(g(lo) > 0.0)) return lo;
   if (!(g(hi) < 0.0)) return hi;
   double a = lo, b = hi, x = fmin(fmax(nu0, lo), hi);
   for (int it = 0; it < 200; ++it) {
     const double gx = g(x);
     if (gx > 0.0) a = x; else if (gx < 0.0) b = x; else return x;
-    const double dg = 1.0 / x - 0.5 * trigamma(0.5 * x);
+    const double dg = 1.0 / x - 0.5 * num::trigamma(0.5 * x);
     double xn = x - gx / dg;
     if (!(xn > a && xn < b)) xn = 0.5 * (a + b);
     if (fabs(xn - x) <= 1e-15 * xn) return xn;
@@ -451,7 +415,7 @@ __global__ __launch_bounds__(kThreads) void mvt_update_kernel(const double* __re
   const double* A = tot + npairs;
   const double sum_u = tot[npairs + P], sum_c1 = tot[npairs + P + 1], sum_c2 = tot[npairs + P + 2];
   // the log-likelihood at the parameters the pass ran with
-  const double ll = events * (((log_gamma(0.5 * (nu + D)) - log_gamma(0.5 * nu)) - 0.5 * D * log(3.14159265358979323846 * nu))
+  const double ll = events * (((num::log_gamma(0.5 * (nu + D)) - num::log_gamma(0.5 * nu)) - 0.5 * D * log(3.14159265358979323846 * nu))
                               - (double)F * par[kLogDet]) - 0.5 * (nu + D) * sum_c2;
   if (nbad || !(fabs(ll) <= 1.79769313486231570815e308)) {
     fail(par, P);
@@ -475,7 +439,7 @@ __global__ __launch_bounds__(kThreads) void mvt_update_kernel(const double* __re
   const double ld = factor(S, P, L, Li);
   if (ld != ld) { fail(par, P); par[kLogLik] = qnan(); return; }
   const double h = 0.5 * (nu + D);
-  const double c = ((1.0 + sum_c1 / events) + digamma(h)) - log(h);
+  const double c = ((1.0 + sum_c1 / events) + num::digamma(h)) - log(h);
   const double nu_new = solve_nu(c, nu, df_lo, df_hi);
   // the relative change of (mu, S, nu)
   double delta = fabs(nu_new - nu) / nu_new;

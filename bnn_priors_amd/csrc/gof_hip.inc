@@ -8,27 +8,29 @@
 //   laplace  log(1/2) - z
 //   t        T = I_x(nu/2, 1/2) / 2, x = nu / (nu + z^2).  With y = 1 - x = z^2 / (nu + z^2), formed from z and not from x,
 //            log front = log(x^(nu/2) y^(1/2) / B(nu/2, 1/2)) = nu/2 log((nu + 1) / (nu + z^2)) + 1/2 log(y (nu + 1)) + log_const:
-//            summary::beta_front's formula (Stirling's remainders only: summary::make_beta's log_const) with its two
-//            logarithms taken of quantities that have one rounding each.  Where summary::beta_cdf would evaluate the
-//            other tail (y < 3 / (nu + 5)): T = 1/2 - front cf(1/2, nu/2; y), cf = summary::beta_fraction as it is; else
-//            lt = log front + log(r / 2), r the even part of the same fraction in (x, y, lambda) (beta_fraction_even: the
-//            plain one loses 1 / y roundings where y is small).  The density is front / z.
+//            num::beta_front's formula (Stirling's remainders only: num::make_beta's log_const, here with
+//            num::stirling_rest) with its two logarithms taken of quantities that have one rounding each.  Where
+//            num::beta_cdf would evaluate the other tail (y < 3 / (nu + 5)): T = 1/2 - front cf(1/2, nu/2; y),
+//            cf = num::beta_fraction as it is; else lt = log front + log(r / 2), r the even part of the same fraction in
+//            (x, y, lambda) (num::beta_fraction_even: the plain one loses 1 / y roundings where y is small).  The density
+//            is front / z.
 //   gennorm  T = Q(1/beta, z^beta) / 2        dgamma  T = Q(a, z) / 2
-// Q(a, x) is the regularised upper incomplete gamma function: for x < a + 1 one minus the series of P, else the modified
-// Lentz evaluation of its continued fraction, both times the prefactor x^a e^-x / Gamma(a), which is kept as a logarithm
+// Q(a, x) is the regularised upper incomplete gamma function: for x < a + 1 one minus the series of P (num::gamma_series),
+// else the modified Lentz evaluation of its continued fraction (num::gamma_fraction), both times the prefactor
+// x^a e^-x / Gamma(a), which is kept as a logarithm
 //   lp = a (log1p(u) - u) + log(a / (2 pi)) / 2 - D(a),  u = (x - a) / a   (a log(x / a) - (x - a) where |u| > 1/2),
 // i.e. a log x - x - lgamma(a) with Stirling's formula applied on paper, so that near x = a, where the three terms are of
 // size a log a and their sum is of size 1, nothing cancels.  D(a) = lgamma(a) - ((a - 1/2) log a - a + log(2 pi) / 2) is
-// fit::log_gamma's series from a >= 10 on and the recurrence D(a) = D(a + 1) + (a + 1/2) log1p(1 / a) - 1 below.
+// num::stirling_rest: num::log_gamma's series from a >= 10 on and a recurrence below.
 //
 //   cdf_kernel     element-wise F, 1 - F, log F, log(1 - F) of arbitrary points for one family
 //   stat_kernel    one pass over the ascending array for up to 6 (family, parameters) records: each value is loaded once
 //                  and every record is evaluated on it.  A tile is kTile consecutive values, thread t takes values t,
 //                  t + 256, ...; workgroup b of blocks(n) takes tiles b, b + blocks, ... in ascending order; a thread's
-//                  sums are compensated (fit::comp_add), a workgroup's threads meet in a fixed tree in LDS.
+//                  sums are compensated (num::comp_add), a workgroup's threads meet in a fixed tree in LDS.
 //   finish_kernel  one workgroup, a thread per record: the workgroups' partials in ascending order
 //   ppf_kernel     model quantiles at the plotting positions (j - 1/2) / K by Newton steps on the log-tail inside a bracket
-//                  (the pattern of summary::beta_inverse), and the type-7 empirical quantiles in summary::quantile_kernel's
+//                  (num::Bracket), and the type-7 empirical quantiles in summary::quantile_kernel's
 //                  arithmetic
 //
 // No atomics, no allocation; tile and grid are functions of n alone, so every sum runs in an order fixed by n.
@@ -45,9 +47,8 @@ constexpr int kPart = SGMCMC_GOF_PART;                 // doubles of one record'
 constexpr int kOut = SGMCMC_GOF_OUT;
 constexpr int kStride = (kMaxRecords + 1) * kPart;     // doubles of one workgroup's partials; [kMaxRecords * kPart]: bad
 constexpr int64_t kMaxN = 0x7fffffffll;
-constexpr int kTerms = 20000;                          // of the series and of the continued fraction, at most
+constexpr int kTerms = 20000;                          // of the gamma series and of its continued fraction, at most
 constexpr int kRootSteps = 200;
-constexpr double kLogHalf = -0.69314718055994530942, kHalfLog2Pi = 0.91893853320467274178;
 static_assert(kTile % kThreads == 0 && (kThreads & (kThreads - 1)) == 0, "tile");
 static_assert(kPart == 8 && kOut == 8, "record layouts");
 
@@ -68,7 +69,7 @@ struct Fam {                // a record and what does not depend on x
   double a;                 // of Q(a, .): 1 / beta, a
   double c;                 // log(a / (2 pi)) / 2 - D(a)
   double lnorm;             // the density's log constant
-  double log_const;         // t: summary::Beta's
+  double log_const;         // t: num::Beta's
 };
 
 inline bool finite_host(double v) { return v - v == 0.0; }
@@ -99,21 +100,6 @@ inline int blocks(int64_t n) {
   return (int)(tiles < kMaxBlocks ? tiles : kMaxBlocks);
 }
 
-__device__ __forceinline__ bool is_finite(double v) { return fabs(v) < INFINITY; }         // false for NaN as well
-
-// D(a) = lgamma(a) - ((a - 1/2) log a - a + log(2 pi) / 2), a > 0
-__device__ double stirling_rest(double a) {
-  double d = 0.0;
-  while (a < 10.0) {                                  // D(a) - D(a + 1) = (a + 1/2) log1p(1 / a) - 1
-    const double v = 1.0 / a;
-    d += v <= 0.5 ? (a + 0.5) * summary::log1p_minus(v) + 0.5 * v : (a + 0.5) * log1p(v) - 1.0;
-    a += 1.0;
-  }
-  const double f = 1.0 / (a * a);                     // fit::log_gamma's series
-  return d + (1.0 / a) * (1.0 / 12 - f * (1.0 / 360 - f * (1.0 / 1260 - f * (1.0 / 1680 - f * (1.0 / 1188
-             - f * (691.0 / 360360 - f * (1.0 / 156)))))));
-}
-
 __device__ Fam prepare(const Rec& r) {
   Fam F;
   F.family = r.family;
@@ -122,14 +108,14 @@ __device__ Fam prepare(const Rec& r) {
   F.scale = r.scale;
   F.a = F.c = F.lnorm = F.log_const = 0.0;
   if (r.family == kT) {
-    // summary::make_beta's log_const, log(a b / (2 pi T)) / 2 + D(T) - D(a) - D(b) at a = nu / 2, b = 1 / 2, T = a + b
+    // num::make_beta's log_const, log(a b / (2 pi T)) / 2 + D(T) - D(a) - D(b) at a = nu / 2, b = 1 / 2, T = a + b
     const double a = 0.5 * r.shape, total = a + 0.5;
-    F.log_const = 0.5 * log(0.5 * a / (6.283185307179586477 * total)) + stirling_rest(total) - stirling_rest(a) -
-                  stirling_rest(0.5);
+    F.log_const = 0.5 * log(0.5 * a / (num::kTwoPi * total)) + num::stirling_rest(total) - num::stirling_rest(a) -
+                  num::stirling_rest(0.5);
   } else if (r.family == kGennorm || r.family == kDgamma) {
     F.a = r.family == kGennorm ? 1.0 / r.shape : r.shape;
-    F.c = 0.5 * log(F.a / 6.283185307179586477) - stirling_rest(F.a);
-    F.lnorm = (r.family == kGennorm ? log(r.shape) : 0.0) + kLogHalf - fit::log_gamma(F.a);
+    F.c = 0.5 * log(F.a / num::kTwoPi) - num::stirling_rest(F.a);
+    F.lnorm = (r.family == kGennorm ? log(r.shape) : 0.0) + num::kLogHalf - num::log_gamma(F.a);
   }
   return F;
 }
@@ -137,71 +123,16 @@ __device__ Fam prepare(const Rec& r) {
 // log Q(a, x) and Q(a, x), x > 0; c = log(a / (2 pi)) / 2 - D(a)
 __device__ void upper_gamma(double a, double x, double c, double* log_q, double* q) {
   const double excess = x - a, u = excess / a;
-  const double lp = (fabs(u) <= 0.5 ? a * summary::log1p_minus(u) : a * log(x / a) - excess) + c;
+  const double lp = (fabs(u) <= 0.5 ? a * num::log1p_minus(u) : a * log(x / a) - excess) + c;
   if (x < a + 1.0) {                                  // P = e^lp sum_k x^k / (a (a + 1) .. (a + k))
-    double ap = a, term = 1.0 / a, sum = term;
-    for (int k = 0; k < kTerms; ++k) {
-      ap += 1.0;
-      term *= x / ap;
-      sum += term;
-      if (term <= 1.1e-16 * sum) break;
-    }
-    const double p = fmin(exp(lp) * sum, 1.0);
+    const double p = fmin(exp(lp) * num::gamma_series(a, x, kTerms), 1.0);
     *q = 1.0 - p;
     *log_q = log1p(-p);
     return;
   }
-  constexpr double tiny = 1e-300;
-  double b = x + 1.0 - a, cc = 1.0 / tiny, d = 1.0 / b, h = d;
-  for (int i = 1; i <= kTerms; ++i) {
-    const double an = -(double)i * ((double)i - a);
-    b += 2.0;
-    d = an * d + b;
-    if (fabs(d) < tiny) d = tiny;
-    cc = b + an / cc;
-    if (fabs(cc) < tiny) cc = tiny;
-    d = 1.0 / d;
-    const double del = d * cc;
-    h *= del;
-    if (fabs(del - 1.0) <= 2.3e-16) break;
-  }
+  const double h = num::gamma_fraction(a, x, kTerms);
   *log_q = lp + log(h);
   *q = exp(lp) * h;
-}
-
-// I_x(a, b) / (x^a y^b / B(a, b)), y = 1 - x, for x below the mean: the EVEN PART of the continued fraction that
-// summary::beta_fraction evaluates (DiDonato & Morris 1992, TOMS 708, BFRAC), in x, y and lambda = (a + b) y - b, each
-// given with one rounding.  The plain fraction forms 1 - (a + b) x / (a + 1) and its likes from x alone: where y is
-// small (df large: y = 5e-4 at df = 1e4, z = 2) they cancel and cost 1 / y roundings, measured 313 eps at df = 1e4; the
-// contraction carries that difference as lambda and loses nothing (measured below 6 eps for df = 0.1 .. 1e4).
-__device__ double beta_fraction_even(double a, double b, double x, double y, double lambda) {
-  const double c = lambda + 1.0, c0 = b / a, c1 = 1.0 / a + 1.0, yp1 = y + 1.0;
-  double n = 0.0, p = 1.0, s = a + 1.0, an = 0.0, bn = 1.0, anp1 = 1.0, bnp1 = c / c1, r = c1 / c;
-  for (int it = 0; it < kTerms; ++it) {
-    n += 1.0;
-    double t = n / a;
-    const double w = n * (b - n) * x;
-    double e = a / s;
-    const double alpha = p * (p + c0) * e * e * (w * x);
-    e = (t + 1.0) / (c1 + t + t);
-    const double beta = n + w / s + e * (c + n * yp1);
-    p = t + 1.0;
-    s += 2.0;
-    t = alpha * an + beta * anp1;
-    an = anp1;
-    anp1 = t;
-    t = alpha * bn + beta * bnp1;
-    bn = bnp1;
-    bnp1 = t;
-    const double r0 = r;
-    r = anp1 / bnp1;
-    if (fabs(r - r0) <= 1e-16 * r) break;
-    an /= bnp1;                                             // rescaled: b_(n + 1) = 1
-    bn /= bnp1;
-    anp1 = r;
-    bnp1 = 1.0;
-  }
-  return r;
 }
 
 struct Tail {
@@ -212,14 +143,14 @@ __device__ Tail tail(const Fam& F, double z) {              // 0 < z < inf
   Tail r;
   switch (F.family) {
     case kNorm: {
-      const double h = 0.5 * (z * z), e = 0.5 * erfcx(z * 0.70710678118654752440);
+      const double h = 0.5 * (z * z), e = 0.5 * erfcx(z * num::kInvSqrt2);
       r.lt = log(e) - h;
       r.T = e * exp(-h);
-      r.lpdf = -h - kHalfLog2Pi;
+      r.lpdf = -h - num::kHalfLog2Pi;
       break;
     }
     case kLaplace:
-      r.lt = kLogHalf - z;
+      r.lt = num::kLogHalf - z;
       r.T = 0.5 * exp(-z);
       r.lpdf = r.lt;
       break;
@@ -229,10 +160,10 @@ __device__ Tail tail(const Fam& F, double z) {              // 0 < z < inf
       const double l1 = fabs(rr) <= 0.5 ? log1p(rr) : log((nu + 1.0) / den);
       const double lfront = 0.5 * nu * l1 + 0.5 * log(y * (nu + 1.0)) + F.log_const;
       if (y < 3.0 / (nu + 5.0)) {                           // x >= (a + 1) / (a + b + 2): the other tail
-        r.T = 0.5 - exp(lfront) * summary::beta_fraction(0.5, 0.5 * nu, y);
+        r.T = 0.5 - exp(lfront) * num::beta_fraction(0.5, 0.5 * nu, y);
         r.lt = log(r.T);
       } else {
-        const double cf = 0.5 * beta_fraction_even(0.5 * nu, 0.5, x, y, nu * (z2 - 1.0) / (2.0 * den));
+        const double cf = 0.5 * num::beta_fraction_even(0.5 * nu, 0.5, x, y, nu * (z2 - 1.0) / (2.0 * den));
         r.T = exp(lfront) * cf;
         r.lt = lfront + log(cf);
       }
@@ -245,7 +176,7 @@ __device__ Tail tail(const Fam& F, double z) {              // 0 < z < inf
       if (!(w < INFINITY)) lq = -INFINITY, q = 0.0;
       else if (w > 0.0) upper_gamma(F.a, w, F.c, &lq, &q);
       else lq = 0.0, q = 1.0;
-      r.lt = lq + kLogHalf;
+      r.lt = lq + num::kLogHalf;
       r.T = 0.5 * q;
       r.lpdf = F.lnorm - w;
       break;
@@ -253,7 +184,7 @@ __device__ Tail tail(const Fam& F, double z) {              // 0 < z < inf
     default: {                                              // kDgamma
       double lq, q;
       upper_gamma(F.a, z, F.c, &lq, &q);
-      r.lt = lq + kLogHalf;
+      r.lt = lq + num::kLogHalf;
       r.T = 0.5 * q;
       r.lpdf = (F.a - 1.0) * log(z) - z + F.lnorm;
       break;
@@ -283,7 +214,7 @@ __device__ Probs probs(const Fam& F, double x) {
   const double d = x - F.loc, z = fabs(d) / F.scale;
   if (z == 0.0) {                                           // exactly one half in every symmetric family
     p.F = p.S = 0.5;
-    p.lF = p.lS = kLogHalf;
+    p.lF = p.lS = num::kLogHalf;
     return p;
   }
   Tail t;
@@ -298,26 +229,18 @@ __device__ Probs probs(const Fam& F, double x) {
   return p;
 }
 
-// the z >= 0 with log T(z) = target <= log(1/2): Newton steps on the log-tail (d lt / dz = -pdf / T), kept inside a
-// bracket that every evaluation narrows; without an upper end yet, a step grows z eightfold at most.  It ends
-// with the first Newton step below 1e-10 z (summary::beta_inverse's rule: its successor would be far below an ulp).
+// the z >= 0 with log T(z) = target <= log(1/2): Newton steps on the log-tail (d lt / dz = -pdf / T) by num::Bracket,
+// without an upper end at first
 __device__ double tail_inverse(const Fam& F, double target) {
-  double lo = 0.0, hi = INFINITY, z = 1.0;
+  num::Bracket br = {0.0, INFINITY};
+  double z = 1.0;
   for (int it = 0; it < kRootSteps; ++it) {
     const Tail t = tail(F, z);
     const double g = t.lt - target;
     if (g == 0.0) return z;
-    if (g > 0.0) lo = z;
-    else hi = z;
-    double next = z + g * exp(t.lt - t.lpdf);
-    if (next == z) break;
-    if (!(hi < INFINITY) && next > 8.0 * z) next = 8.0 * z;     // (a flat log-tail at z sends the step anywhere)
-    const bool newton = next > lo && next < hi;
-    if (!newton) next = hi < INFINITY ? 0.5 * (lo + hi) : 2.0 * z;
-    if (next == lo || next == hi) break;
-    const bool last = newton && fabs(next - z) <= 1e-10 * z;
-    z = next;
-    if (last) break;
+    if (g > 0.0) br.lo = z;
+    else br.hi = z;
+    if (!br.advance(z, z + g * exp(t.lt - t.lpdf))) break;
   }
   return z;
 }
@@ -376,7 +299,7 @@ __global__ __launch_bounds__(kThreads) void stat_kernel(const T* __restrict__ x,
       const int64_t idx = tile * kTile + (int64_t)j * kThreads + t;
       if (idx >= n) break;
       const double v = (double)x[idx];
-      if (!is_finite(v)) {
+      if (!num::is_finite(v)) {
         ++bad;
         continue;
       }
@@ -389,8 +312,8 @@ __global__ __launch_bounds__(kThreads) void stat_kernel(const T* __restrict__ x,
           const double dp = above - p.F, dm = p.F - below, e = p.F - centre;
           if (dp > acc[f][kDp]) acc[f][kDp] = dp, acc[f][kIp] = i;      // strict: the smallest index of a thread's walk
           if (dm > acc[f][kDm]) acc[f][kDm] = dm, acc[f][kIm] = i;
-          fit::comp_add(acc[f][kSw], acc[f][kCw], e * e);
-          fit::comp_add(acc[f][kSa], acc[f][kCa], odd * p.lF + rest * p.lS);
+          num::comp_add(acc[f][kSw], acc[f][kCw], e * e);
+          num::comp_add(acc[f][kSa], acc[f][kCa], odd * p.lF + rest * p.lS);
         }
       }
     }
@@ -408,9 +331,9 @@ __global__ __launch_bounds__(kThreads) void stat_kernel(const T* __restrict__ x,
           const int o = t + s;
           take_max(red[kDp][t], red[kIp][t], red[kDp][o], red[kIp][o]);
           take_max(red[kDm][t], red[kIm][t], red[kDm][o], red[kIm][o]);
-          fit::comp_add(red[kSw][t], red[kCw][t], red[kSw][o]);
+          num::comp_add(red[kSw][t], red[kCw][t], red[kSw][o]);
           red[kCw][t] += red[kCw][o];
-          fit::comp_add(red[kSa][t], red[kCa][t], red[kSa][o]);
+          num::comp_add(red[kSa][t], red[kCa][t], red[kSa][o]);
           red[kCa][t] += red[kCa][o];
           if (f == 0) sbad[t] += sbad[o];
         }
@@ -423,7 +346,7 @@ __global__ __launch_bounds__(kThreads) void stat_kernel(const T* __restrict__ x,
 }
 
 // a compensated sum's value; an infinite sum (log 0 of a point outside the support) stays infinite
-__device__ __forceinline__ double comp_value(double s, double c) { return is_finite(s) ? s + c : s; }
+__device__ __forceinline__ double comp_value(double s, double c) { return num::is_finite(s) ? s + c : s; }
 
 // out [count][kOut]: D, D+, D-, the 1-based index of the supremum, x there, W^2, A^2, the number of non-finite inputs
 template <typename T>
@@ -437,9 +360,9 @@ __global__ __launch_bounds__(64) void finish_kernel(const T* __restrict__ x, int
     const double* __restrict__ p = part + (int64_t)b * kStride + f * kPart;
     take_max(dp, ip, p[kDp], p[kIp]);
     take_max(dm, im, p[kDm], p[kIm]);
-    fit::comp_add(sw, cw, p[kSw]);
+    num::comp_add(sw, cw, p[kSw]);
     cw += p[kCw];
-    fit::comp_add(sa, ca, p[kSa]);
+    num::comp_add(sa, ca, p[kSa]);
     ca += p[kCa];
     bad += part[(int64_t)b * kStride + kMaxRecords * kPart];
   }

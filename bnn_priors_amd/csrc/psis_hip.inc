@@ -318,21 +318,6 @@ __global__ __launch_bounds__(kLanes) void finish_kernel(const T* __restrict__ ta
 
 constexpr int kTot = 256;
 
-// the sum of f(i), i < N, in an order fixed by N: thread t adds i = t, t + kTot, ... ascending, then a tree over threads
-template <typename F>
-__device__ double block_sum(int64_t N, double* sh, F f) {
-  double a = 0.0;
-  for (int64_t i = threadIdx.x; i < N; i += kTot) a = __dadd_rn(a, f(i));
-  __syncthreads();
-  sh[threadIdx.x] = a;
-  __syncthreads();
-  for (int w = kTot / 2; w > 0; w /= 2) {
-    if ((int)threadIdx.x < w) sh[threadIdx.x] = __dadd_rn(sh[threadIdx.x], sh[threadIdx.x + w]);
-    __syncthreads();
-  }
-  return sh[0];
-}
-
 __global__ __launch_bounds__(kTot) void totals_kernel(const double* __restrict__ pw, int64_t N, double threshold,
                                                       double* __restrict__ out) {
   __shared__ double sh[kTot];
@@ -344,19 +329,19 @@ __global__ __launch_bounds__(kTot) void totals_kernel(const double* __restrict__
   double sums[5];
   for (int k = 0; k < 5; ++k) {
     const double* __restrict__ v = pw + (int64_t)rows[k] * N;
-    sums[k] = block_sum(N, sh, [&](int64_t i) { return v[i]; });
+    sums[k] = num::block_sum<kTot>(N, sh, [&](int64_t i) { return v[i]; });
   }
   double se[2];
   for (int k = 0; k < 2; ++k) {                    // se of elpd_loo and of elpd_waic: two passes
     const double* __restrict__ v = pw + (int64_t)(k == 0 ? 1 : 5) * N;
     const double mean = sums[k == 0 ? 0 : 3] / dN;
-    const double ssq = block_sum(N, sh, [&](int64_t i) {
+    const double ssq = num::block_sum<kTot>(N, sh, [&](int64_t i) {
       const double d = __dsub_rn(v[i], mean);
       return __dmul_rn(d, d);
     });
     se[k] = sqrt(__dmul_rn(dN, ssq / __dsub_rn(dN, 1.0)));
   }
-  const double bad = block_sum(N, sh, [&](int64_t i) { return pw[i] > threshold ? 1.0 : 0.0; });
+  const double bad = num::block_sum<kTot>(N, sh, [&](int64_t i) { return pw[i] > threshold ? 1.0 : 0.0; });
   double mx = -INFINITY;
   int seen = 0;
   for (int64_t i = threadIdx.x; i < N; i += kTot) {

@@ -119,7 +119,7 @@ __global__ __launch_bounds__(kThreads) void gram_kernel(const T* __restrict__ f,
 #pragma unroll
       for (int i = 0; i < kBlk; ++i)
 #pragma unroll
-        for (int j = 0; j < kBlk; ++j) fit::comp_add(acc[i][j], comp[i][j], ta[i][j]);
+        for (int j = 0; j < kBlk; ++j) num::comp_add(acc[i][j], comp[i][j], ta[i][j]);
     }
   }
   __syncthreads();
@@ -140,7 +140,7 @@ __global__ __launch_bounds__(kThreads) void gram_kernel(const T* __restrict__ f,
         const int a = bi * kBlk + i, b = bj * kBlk + j;
         if (a < order && b <= a) {
           double s = sf[e * (kBlk * kBlk) + i * kBlk + j], c = 0.0;
-          for (int p = 1; p < S; ++p) fit::comp_add(s, c, sf[(p * nb + e) * (kBlk * kBlk) + i * kBlk + j]);
+          for (int p = 1; p < S; ++p) num::comp_add(s, c, sf[(p * nb + e) * (kBlk * kBlk) + i * kBlk + j]);
           out[a * (a + 1) / 2 + b] = s + c;
         }
       }
@@ -177,7 +177,7 @@ __global__ __launch_bounds__(kFactorThreads) void factor_kernel(const double* __
 #pragma unroll
       for (int q = 0; q < kBatch; ++q)
 #pragma unroll
-        for (int i = 0; i < kOwn; ++i) fit::comp_add(s[i], c[i], val[q][i]);
+        for (int i = 0; i < kOwn; ++i) num::comp_add(s[i], c[i], val[q][i]);
     }
 #pragma unroll
     for (int i = 0; i < kOwn; ++i) {
@@ -248,7 +248,7 @@ __global__ __launch_bounds__(kFactorThreads) void factor_kernel(const double* __
     __syncthreads();
   }
   if (bad) {
-    const double nan = fit::qnan();
+    const double nan = num::qnan();
     if (t < kN && t != kYY) state[t] = nan;
     for (int k = t; k < F; k += kFactorThreads) state[off_b(F) + k] = nan;
     for (int k = t; k < F * F; k += kFactorThreads)

@@ -10,7 +10,7 @@
 //                    one partial per workgroup.
 //   rows_kernel      everything that is O(E) per entry: 16 entries x 16 sample slices per workgroup (a 128-byte run of
 //                    the [E][K] table per load).  Pass 1: the predictive mean; pass 2: the variances and, with y, the
-//                    squared error, the log density (calib::lse_add1 per slice, merged on the slices' maximum), the PIT
+//                    squared error, the log density (num::lse_add1 per slice, merged on the slices' maximum), the PIT
 //                    and the CRPS' first term; it then adds the entry's S pair partials in order and finishes the CRPS.
 //   quantile_kernel  F(q) = p by a safeguarded secant (Illinois) inside the component-quantile hull, bisecting whenever
 //                    a step fails to halve the bracket; the same 16 x 16 layout, every F a slice-wise sum.
@@ -34,30 +34,16 @@ static_assert(kEntries * kSlices == 256 && 2 * kTile == 256 && kMaxLevels == kPi
 static_assert(kTile == SGMCMC_GMIX_TILE && kMaxSamples == SGMCMC_GMIX_MAX_SAMPLES &&
               kMaxQuantiles == SGMCMC_GMIX_MAX_QUANTILES && kMaxLevels == SGMCMC_PIT_MAX_LEVELS, "the header's limits");
 
-constexpr double kInvSqrt2 = 0.70710678118654752440;
-constexpr double kInvSqrtPi = 0.56418958354775628695;
-constexpr double kInvSqrt2Pi = 0.39894228040143267794;
-constexpr double kHalfLog2Pi = 0.91893853320467274178;
-
-__device__ __forceinline__ double quiet_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
+using num::comp_add;
 
 // A(m, s) = m erf(m / (s sqrt 2)) + 2 s phi(m / s) = E|X| of X ~ Normal(m, s)
 __device__ __forceinline__ double abs_moment(double m, double s) {
   const double z = m / s;
-  return m * erf(z * kInvSqrt2) + 2.0 * s * (kInvSqrt2Pi * exp(-0.5 * (z * z)));
+  return m * erf(z * num::kInvSqrt2) + 2.0 * s * (num::kInvSqrt2Pi * exp(-0.5 * (z * z)));
 }
 
 // Phi(z) = erfc(-z / sqrt 2) / 2: both tails keep their relative accuracy
-__device__ __forceinline__ double normal_cdf(double z) { return 0.5 * erfc(-(z * kInvSqrt2)); }
-
-using uncert::comp_add;
-
-// a + b exactly: the rounded sum, and what the rounding lost (Knuth)
-__device__ __forceinline__ double two_sum(double a, double b, double& err) {
-  const double s = a + b, bb = s - a;
-  err = (a - (s - bb)) + (b - bb);
-  return s;
-}
+__device__ __forceinline__ double normal_cdf(double z) { return 0.5 * erfc(-(z * num::kInvSqrt2)); }
 
 inline int tiles_of(int E) { return (E + kTile - 1) / kTile; }
 
@@ -118,7 +104,7 @@ __global__ __launch_bounds__(256) void pair_kernel(const double* __restrict__ me
   for (int h = 128; h > 0; h >>= 1) {
     if (t < h) {
       double err;
-      red_s[t] = two_sum(red_s[t], red_s[t + h], err);
+      red_s[t] = num::two_sum(red_s[t], red_s[t + h], err);
       red_c[t] = (red_c[t] + red_c[t + h]) + err;
     }
     __syncthreads();
@@ -208,10 +194,10 @@ __global__ __launch_bounds__(256) void rows_kernel(const double* __restrict__ me
       comp_add(a1, a1_c, abs_moment(m, sg));
       comp_add(sgs, sgs_c, sg);
       comp_add(pit, pit_c, normal_cdf(z));
-      calib::lse_add1(lm, ls, (-0.5 * (z * z) - log(sg)) - kHalfLog2Pi);
+      num::lse_add1(lm, ls, (-0.5 * (z * z) - log(sg)) - num::kHalfLog2Pi);
     }
   }
-  const double nan = quiet_nan();
+  const double nan = num::qnan();
   const double alea = slice_sum(bs, bc, va, va_c) / (double)E;
   const double epi = slice_sum(bs, bc, ve, ve_c) / (double)E;
   const bool writer = live && q == 0;
@@ -229,7 +215,7 @@ __global__ __launch_bounds__(256) void rows_kernel(const double* __restrict__ me
   const double top = slice_extreme<true>(bs, lm);
   const double part = (lm == -INFINITY || ls == 0.0) ? ls : ls * exp(lm - top);
   const double total = slice_sum(bs, bc, part, 0.0);
-  const double lpd = calib::lse_log_mean(top, total, E);
+  const double lpd = num::lse_log_mean(top, total, E);
   // the pair partials of this entry, dealt to the slices in order
   double ps = 0.0, pc = 0.0;
   for (int j = q; j < S; j += kSlices) comp_add(ps, pc, partial[k * S + j]);
@@ -239,7 +225,7 @@ __global__ __launch_bounds__(256) void rows_kernel(const double* __restrict__ me
     o_sq[k] = bad ? nan : de * de;
     o_lpd[k] = bad ? nan : lpd;
     o_pit[k] = bad ? nan : u;
-    o_crps[k] = bad ? nan : first / (double)E - (pairs + sg_sum * kInvSqrtPi) / ((double)E * (double)E);
+    o_crps[k] = bad ? nan : first / (double)E - (pairs + sg_sum * num::kInvSqrtPi) / ((double)E * (double)E);
   }
 }
 
@@ -315,7 +301,7 @@ __global__ __launch_bounds__(256) void quantile_kernel(const double* __restrict_
       bisect = !bisect && (hi - lo) > 0.5 * width;            // a step that did not halve the bracket: bisect next
     }
   }
-  if (live && q == 0) out[item] = bad ? quiet_nan() : (r_lo <= r_hi ? lo : hi);
+  if (live && q == 0) out[item] = bad ? num::qnan() : (r_lo <= r_hi ? lo : hi);
 }
 
 // pit: column `col` holds n values at pit[col * col_stride + i * elem_stride]; perm = sgmcmc_stable_order of the columns.

@@ -1720,6 +1720,9 @@ int sgmcmc_debug_normals(float* out, int64_t start, int64_t n, uint64_t seed, ui
 #endif
 #include "pool_hip.inc"
 #include "augment_hip.inc"
+// The fp64 statistics kernels: numerics_hip.inc (namespace num) has the arithmetic they share.  A file below depends on it
+// and on data layout only (diag::Seqs, rankdiag::Stats, calib::kMaxRows / kMaxClasses): after calib, diag and rank.
+#include "numerics_hip.inc"
 // calibration / OOD-detection metrics of a posterior ensemble (evaluation side, fp64)
 #include "calib_hip.inc"
 // ... and the ensemble's uncertainty: entropy decomposition, disagreement, proper scores, risk-coverage curves (fp64)
@@ -1739,12 +1742,10 @@ int sgmcmc_debug_normals(float* out, int64_t start, int64_t n, uint64_t seed, ui
 // the data-driven priors fitted to stacks of weight samples: moments, multivariate-t EM, element-wise families (fp64)
 #include "fit_hip.inc"
 // ... and the correlation between the rows, columns or channels of such a stack: means, the centred Gram matrix on the
-// fp64 matrix pipe, cov / corr and the off-diagonal statistics (fp64; after fit_hip.inc: it uses fit::comp_add)
+// fp64 matrix pipe, cov / corr and the off-diagonal statistics (fp64)
 #include "corr_hip.inc"
-// ... and how well the fitted families describe them: distribution functions in log space, KS / CvM / AD, Q-Q (fp64;
-// after fit_hip.inc as well as summary_hip.inc: it uses fit::comp_add and fit::log_gamma)
+// ... and how well the fitted families describe them: distribution functions in log space, KS / CvM / AD, Q-Q (fp64)
 #include "gof_hip.inc"
-// ... and whether a chain samples at its temperature: chi-square tails at any size, intervals, coverage, EWMA (fp64;
-// after gof_hip.inc: it uses gof::stirling_rest, summary::log1p_minus and fit::comp_add)
+// ... and whether a chain samples at its temperature: chi-square tails at any size, intervals, coverage, EWMA (fp64)
 #include "temper_hip.inc"
 #include "raob_hip.inc"

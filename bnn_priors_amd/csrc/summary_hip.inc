@@ -25,8 +25,9 @@
 //   quantile_kernel  the type-7 quantile of one probability from two rows of the sorted array, in rankdiag's arithmetic
 //   hdi_kernel       lane = quantity: the narrowest window of k + 1 consecutive order statistics, first minimum
 //   mcse_kernel      mcse_mean and mcse_sd from the moments and the two ESS; the constant-column rule
-//   mcse_quantile_kernel   lane = quantity: alpha, beta from ess_q, the inverse regularised incomplete beta function at
-//                    Phi(-1) and Phi(1), the two ranks, and half the distance of their order statistics
+//   mcse_quantile_kernel   lane = quantity: alpha, beta from ess_q, the inverse regularised incomplete beta function
+//                    (num::beta_inverse) at Phi(-1) and Phi(1), the two ranks, and half the distance of their order
+//                    statistics
 //
 // No atomics; every sum in an order fixed by N; a quantity's result is a function of its own column only, whatever the
 // grid, the tile or the chunk.
@@ -63,7 +64,6 @@ inline bool make_seqs(int64_t chain_stride, int64_t draw_stride, int chains, int
 }
 
 __device__ __forceinline__ double plus_zero(double v) { return v == 0.0 ? 0.0 : v; }      // -0.0 is written as +0.0
-__device__ __forceinline__ bool is_finite(double v) { return fabs(v) < INFINITY; }         // false for NaN as well
 
 template <typename T>
 __global__ __launch_bounds__(kSortThreads) void sort_kernel(const T* __restrict__ x, diag::Seqs A, int64_t Q, int N,
@@ -85,7 +85,7 @@ __global__ __launch_bounds__(kSortThreads) void sort_kernel(const T* __restrict_
       if (q0 + c < Q) {
         const int j = i / A.n, s = i - j * A.n;
         v = plus_zero((double)x[diag::seq_offset(A, j) + (int64_t)s * A.draw_stride + q0 + c]);
-        if (!is_finite(v)) bad[c] = 1;            // every writer stores the same value
+        if (!num::is_finite(v)) bad[c] = 1;            // every writer stores the same value
       }
     }
     tile[e] = v;
@@ -146,7 +146,7 @@ __global__ __launch_bounds__(kThreads) void moments_kernel(const T* __restrict__
   if (live) {
     for (int i = way; i < N; i += kWays) {
       const double v = draw(xq, A, i);
-      finite = finite && is_finite(v);
+      finite = finite && num::is_finite(v);
       constant = constant && v == first;
       p = __dadd_rn(p, v);
     }
@@ -237,131 +237,6 @@ __global__ __launch_bounds__(kThreads) void mcse_kernel(const double* __restrict
   mcse_sd[q] = sqrt(__ddiv_rn(__ddiv_rn(__ddiv_rn(excess, es), v2), 4.0));
 }
 
-// ---- the regularised incomplete beta function I_x(a, b) and its inverse, fp64 -------------------------------------------
-// I_x(a, b) = front(x) cf(x; a, b) / a for x < (a + 1) / (a + b + 2), else 1 - front(x) cf(1 - x; b, a) / b, with
-// front(x) = x^a (1 - x)^b / B(a, b) and cf the continued fraction 26.5.8 of Abramowitz and Stegun by the modified Lentz
-// recurrence.  The accuracy of I at a, b of 10^4 is that of log front: lgamma(a + b) - lgamma(a) - lgamma(b) loses
-// log10(a log a) digits, so Stirling's formula is applied to the three of them on paper and only its remainders D are
-// evaluated (TOMS 708's brcomp),
-//   log front = a l(u) + b l(w) + log(a b / (2 pi T)) / 2 + D(T) - D(a) - D(b),   l(u) = log1p(u) - u,
-//   T = a + b,  u = (x T - a) / a,  w = -(x T - a) / b   (a u + b w = 0 exactly: the first-order terms cancel on paper),
-//   D(z) = lgamma(z) - ((z - 1/2) log z - z + log(2 pi) / 2) = 1/(12 z) - 1/(360 z^3) + ...: the series from
-//   z = kStirling on, the difference itself below (where lgamma is small and the difference costs nothing),
-// and T carried as the rounded sum and its rounding error so that x T - a is formed with one rounding.
-
-constexpr double kStirling = 20.0;
-constexpr int kFractionTerms = 4000;
-constexpr int kRootSteps = 200;
-
-__device__ __forceinline__ double stirling_rest(double z) {
-  if (z < kStirling) return lgamma(z) - ((z - 0.5) * log(z) - z + 0.91893853320467274178);
-  const double r = 1.0 / z, r2 = r * r;
-  return r * (1.0 / 12.0 - r2 * (1.0 / 360.0 - r2 * (1.0 / 1260.0 - r2 * (1.0 / 1680.0 - r2 * (1.0 / 1188.0 - r2 * (691.0 / 360360.0))))));
-}
-
-// log1p(u) - u, u > -1: for |u| <= 0.5 as -r u + 2 r^3 (1/3 + r^2/5 + r^4/7 + ...), r = u / (2 + u), which has no
-// cancellation (-r u is the whole second-order term)
-__device__ __forceinline__ double log1p_minus(double u) {
-  if (fabs(u) > 0.5) return log1p(u) - u;
-  const double r = u / (2.0 + u), r2 = r * r;
-  double power = 1.0, series = 1.0 / 3.0;
-  for (int k = 5; k < 80; k += 2) {
-    power *= r2;
-    const double term = power / (double)k;
-    series += term;
-    if (term < 1e-18 * series) break;
-  }
-  return 2.0 * r * r2 * series - r * u;
-}
-
-struct Beta {               // a, b and what does not depend on x
-  double a, b, total, total_err, log_const;
-};
-
-__device__ __forceinline__ Beta make_beta(double a, double b) {
-  Beta B;
-  B.a = a;
-  B.b = b;
-  B.total = a + b;
-  const double bv = B.total - a;                                  // two-sum: total + total_err = a + b exactly
-  B.total_err = (a - (B.total - bv)) + (b - bv);
-  B.log_const = 0.5 * log(a * b / (6.283185307179586477 * B.total)) + stirling_rest(B.total) - stirling_rest(a) -
-                stirling_rest(b);
-  return B;
-}
-
-// x^a (1 - x)^b / B(a, b), 0 < x < 1
-__device__ __forceinline__ double beta_front(const Beta& B, double x) {
-  const double excess = fma(x, B.total, -B.a) + x * B.total_err;      // x T - a
-  const double u = excess / B.a, w = -excess / B.b;
-  if (!(u > -1.0 && w > -1.0)) return 0.0;
-  return exp(B.a * log1p_minus(u) + B.b * log1p_minus(w) + B.log_const);
-}
-
-__device__ double beta_fraction(double a, double b, double x) {
-  constexpr double tiny = 1e-300;
-  const double qab = a + b, qap = a + 1.0, qam = a - 1.0;
-  double c = 1.0, d = 1.0 - qab * x / qap;
-  if (fabs(d) < tiny) d = tiny;
-  d = 1.0 / d;
-  double h = d;
-  for (int m = 1; m <= kFractionTerms; ++m) {
-    const double m2 = 2.0 * m;
-    double aa = m * (b - m) * x / ((qam + m2) * (a + m2));
-    d = 1.0 + aa * d;
-    if (fabs(d) < tiny) d = tiny;
-    c = 1.0 + aa / c;
-    if (fabs(c) < tiny) c = tiny;
-    d = 1.0 / d;
-    h *= d * c;
-    aa = -(a + m) * (qab + m) * x / ((a + m2) * (qap + m2));
-    d = 1.0 + aa * d;
-    if (fabs(d) < tiny) d = tiny;
-    c = 1.0 + aa / c;
-    if (fabs(c) < tiny) c = tiny;
-    d = 1.0 / d;
-    const double del = d * c;
-    h *= del;
-    if (fabs(del - 1.0) <= 2.3e-16) break;
-  }
-  return h;
-}
-
-// I_x(a, b) and the density x^(a-1) (1 - x)^(b-1) / B(a, b), 0 < x < 1
-__device__ double beta_cdf(const Beta& B, double x, double* density) {
-  const double front = beta_front(B, x);
-  *density = front / (x * (1.0 - x));
-  if (x < (B.a + 1.0) / (B.total + 2.0)) return front * beta_fraction(B.a, B.b, x) / B.a;
-  return 1.0 - front * beta_fraction(B.b, B.a, 1.0 - x) / B.b;
-}
-
-// the x in (0, 1) with I_x(a, b) = P, 0 < P < 1, a, b > 0: Newton steps kept inside a bracket that every evaluation
-// narrows (a bisection step whenever Newton leaves it or the density vanishes).
-// It starts `sds` standard deviations of the beta distribution from its mean (the normal approximation of the root:
-// P = Phi(sds)) and ends with the first Newton step below 1e-10 x: its successor would be about 1e-20 x C with
-// C = |f''| x / (2 f'), which is x / sd <= sqrt(a + b) that close to the mean -- far below an ulp.
-__device__ double beta_inverse(const Beta& B, double P, double sds) {
-  const double mean = B.a / B.total;
-  double lo = 0.0, hi = 1.0, x = mean + sds * sqrt(mean * (B.b / B.total) / (B.total + 1.0));
-  if (!(x > lo && x < hi)) x = mean;
-  for (int it = 0; it < kRootSteps; ++it) {
-    double density;
-    const double f = beta_cdf(B, x, &density) - P;
-    if (f == 0.0) return x;
-    if (f < 0.0) lo = x;
-    else hi = x;
-    double next = x - f / density;
-    if (next == x) break;                                              // a Newton step below half an ulp
-    const bool newton = next > lo && next < hi;
-    if (!newton) next = 0.5 * (lo + hi);
-    if (next == lo || next == hi) break;                               // the bracket has no interior left
-    const bool last = newton && fabs(next - x) <= 1e-10 * x;
-    x = next;
-    if (last) break;
-  }
-  return x;
-}
-
 __global__ __launch_bounds__(kThreads) void mcse_quantile_kernel(const double* __restrict__ sorted, int N, double p,
                                                                  const double* __restrict__ ess_q, int64_t Q,
                                                                  double* __restrict__ mcse, double* __restrict__ a_out,
@@ -374,9 +249,9 @@ __global__ __launch_bounds__(kThreads) void mcse_quantile_kernel(const double* _
   int lo = -1, hi = -1;
   if (ess > 0.0 && ess < INFINITY) {
     const double alpha = __dadd_rn(__dmul_rn(ess, p), 1.0), beta = __dadd_rn(__dmul_rn(ess, __dsub_rn(1.0, p)), 1.0);
-    const Beta B = make_beta(alpha, beta);                             // alpha, beta >= 1 and finite
-    a = beta_inverse(B, kLowerTail, -1.0);
-    b = beta_inverse(B, kUpperTail, 1.0);
+    const num::Beta B = num::make_beta(alpha, beta);                             // alpha, beta >= 1 and finite
+    a = num::beta_inverse(B, kLowerTail, -1.0);
+    b = num::beta_inverse(B, kUpperTail, 1.0);
     if (a == a && b == b) {
       const double fl = floor(__dmul_rn(a, Nd)), ce = ceil(__dmul_rn(b, Nd));
       lo = min(max((int)fmax(fl, 1.0) - 1, 0), N - 1);                 // in range whatever the root search returned

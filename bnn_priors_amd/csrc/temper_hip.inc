@@ -6,7 +6,7 @@
 // tails(a, r): log P(a, a r), log Q(a, a r), P, Q and the prefactor's logarithm.  ONE of the two tails is evaluated, in log
 // space, by the method of its region, and the other derived from it (1 - small, log1p(-small)); the evaluated one is the
 // small one except in the band a <= x < a + 1 (below).  With u = r - 1 (exact for 1/2 <= r <= 2: the point is never formed
-// as x - a) and l = log1p(u) - u (summary::log1p_minus, no cancellation near r = 1):
+// as x - a) and l = log1p(u) - u (num::log1p_minus, no cancellation near r = 1):
 //   uniform   a >= kTemmeA = 100 and |u| <= kTemmeU = 0.3: Temme's uniform expansion (SIAM J. Math. Anal. 10 (1979); DLMF
 //             8.12.3-10; the form DiDonato & Morris use in TOMS 654),
 //                 Q = erfc(y) / 2 + S,  P = erfc(-y) / 2 - S,  S = e^(-h) / sqrt(2 pi a) sum_k c_k(eta) a^-k,
@@ -17,9 +17,9 @@
 //             (mu = u as a series in eta; gamma_k = -c_(k-1)'(0), Stirling's coefficients) and cut where the rest is below
 //             3e-19 * 100^k at |eta| = 0.34 (eta(-0.3) = -0.337, eta(0.3) = 0.274); the first term left out, c_9 a^-9, is
 //             below 6e-22 at a = 100.
-//   series    elsewhere, x < a + 1:  P = e^lp sum_k x^k / (a (a + 1) .. (a + k))      (gof::upper_gamma's two methods
-//   fraction  elsewhere, x >= a + 1: Q = e^lp * the modified Lentz fraction            with its prefactor lp)
-//             lp = a l + log(a / (2 pi)) / 2 - D(a)   (a log r - a u where |u| > 1/2), D = gof::stirling_rest.
+//   series    elsewhere, x < a + 1:  P = e^lp sum_k x^k / (a (a + 1) .. (a + k))      (num::gamma_series and
+//   fraction  elsewhere, x >= a + 1: Q = e^lp * the modified Lentz fraction            num::gamma_fraction)
+//             lp = a l + log(a / (2 pi)) / 2 - D(a)   (a log r - a u where |u| > 1/2), D = num::stirling_rest.
 //             Both need O(sqrt a) terms near x = a; outside the uniform region that is at most 8.5 sqrt(100) terms for
 //             a < 100 and about 37 / 0.3 terms for |u| > 0.3 (measured: at most 99 at a = 1e9, 58 at a = 1e3), so kTerms
 //             caps a loop that has ended long before.
@@ -37,10 +37,10 @@
 //   tails_kernel     element-wise, one thread per (step, tensor): r = est / temperature, the four values above
 //   quantile_kernel  one thread per (tensor, entry): the r with log tail(a, r) = t by Newton steps on the log-tail in r
 //                    (d log P / dr = e^(lp - log r - log P)) from the Wilson-Hilferty point, inside a bracket that every
-//                    evaluation narrows, kRootSteps at most (gof::tail_inverse's pattern).  The iterate IS the returned
+//                    evaluation narrows, kRootSteps at most (num::Bracket).  The iterate IS the returned
 //                    r = x / a and the tail is evaluated at u = r - 1, so the bound carries one rounding.
 //   steps_kernel     one thread per step, the tensors in ascending order: the number of tensors with lower <= r <= upper
-//                    per level, Cochran's weighted mean and standard error (compensated sums, fit::comp_add), and the
+//                    per level, Cochran's weighted mean and standard error (compensated sums, num::comp_add), and the
 //                    per-tensor coverage over all steps as INTEGER counts (a wave's ballot, gathered per workgroup in LDS,
 //                    one global integer atomic per workgroup, tensor and level: exact, hence independent of the order)
 //   ewma_kernel      y_0 = x_0, y_t = (1 - alpha) x_t + alpha y_(t-1) as a scan of the affine maps y -> A y + B: one
@@ -59,7 +59,6 @@ constexpr int kTerms = 2000;                           // of the series and of t
 constexpr int kRootSteps = 100;
 constexpr int kStepBlocks = 256, kLdsCounts = 4096;     // of steps_kernel: workgroups at most; counts kept in LDS
 constexpr double kTemmeA = SGMCMC_TEMPER_UNIFORM_A, kTemmeU = SGMCMC_TEMPER_UNIFORM_U;
-constexpr double kTwoPi = 6.283185307179586477, kLogHalf = -0.69314718055994530942;
 static_assert(kScan == kThreads && (kScan & (kScan - 1)) == 0, "scan");
 
 constexpr int kOrders = 9;
@@ -134,10 +133,10 @@ __device__ Tails tails(double a, double r) {
     t.lp = 0.0, t.p = 1.0, t.lq = -INFINITY, t.q = 0.0, t.front = -INFINITY;
     return t;
   }
-  const double c = 0.5 * log(a / kTwoPi) - gof::stirling_rest(a);
+  const double c = 0.5 * log(a / num::kTwoPi) - num::stirling_rest(a);
   const double u = r - 1.0;
   const bool near = fabs(u) <= 0.5;
-  const double l = near ? summary::log1p_minus(u) : 0.0;
+  const double l = near ? num::log1p_minus(u) : 0.0;
   t.front = (near ? a * l : a * log(r) - a * u) + c;
   double small, lsmall;
   bool upper;
@@ -145,37 +144,18 @@ __device__ Tails tails(double a, double r) {
     const double h = -(a * l), y = sqrt(h);
     double eta = sqrt(-2.0 * l);
     if (u < 0.0) eta = -eta;
-    const double s = temme_sum(eta, a) / sqrt(kTwoPi * a);
+    const double s = temme_sum(eta, a) / sqrt(num::kTwoPi * a);
     upper = u >= 0.0;
     const double w = 0.5 * erfcx(y) + (upper ? s : -s);
     lsmall = log(w) - h;
     small = w * exp(-h);
   } else if (x < a + 1.0) {
-    double ap = a, term = 1.0 / a, sum = term;
-    for (int k = 0; k < kTerms; ++k) {
-      ap += 1.0;
-      term *= x / ap;
-      sum += term;
-      if (term <= 1.1e-16 * sum) break;
-    }
+    const double sum = num::gamma_series(a, x, kTerms);
     upper = false;
     lsmall = t.front + log(sum);
     small = exp(t.front) * sum;
   } else {
-    constexpr double tiny = 1e-300;
-    double b = x + 1.0 - a, cc = 1.0 / tiny, d = 1.0 / b, h = d;
-    for (int i = 1; i <= kTerms; ++i) {
-      const double an = -(double)i * ((double)i - a);
-      b += 2.0;
-      d = an * d + b;
-      if (fabs(d) < tiny) d = tiny;
-      cc = b + an / cc;
-      if (fabs(cc) < tiny) cc = tiny;
-      d = 1.0 / d;
-      const double del = d * cc;
-      h *= del;
-      if (fabs(del - 1.0) <= 2.3e-16) break;
-    }
+    const double h = num::gamma_fraction(a, x, kTerms);
     upper = true;
     lsmall = t.front + log(h);
     small = exp(t.front) * h;
@@ -201,23 +181,15 @@ __device__ double tail_inverse(double a, double target, bool upper) {
     r = upper ? 1.0 : exp((target + lgamma(a + 1.0)) / a) / a;       // P ~ x^a / Gamma(a + 1) at small x
     if (!(r > 0.0)) r = 1e-300;
   }
-  double lo = 0.0, hi = INFINITY;
+  num::Bracket br = {0.0, INFINITY};
   for (int it = 0; it < kRootSteps; ++it) {
     const Tails t = tails(a, r);
     const double lt = upper ? t.lq : t.lp, g = lt - target;
     if (g == 0.0) return r;
-    if ((g > 0.0) != upper) hi = r;                       // P rises with r, Q falls
-    else lo = r;
+    if ((g > 0.0) != upper) br.hi = r;                    // P rises with r, Q falls
+    else br.lo = r;
     const double step = g * exp(lt - (t.front - log(r)));
-    double next = upper ? r + step : r - step;
-    if (next == r) break;
-    if (!(hi < INFINITY) && next > 8.0 * r) next = 8.0 * r;
-    const bool newton = next > lo && next < hi;
-    if (!newton) next = hi < INFINITY ? 0.5 * (lo + hi) : 2.0 * r;
-    if (next == lo || next == hi) break;
-    const bool last = newton && fabs(next - r) <= 1e-10 * r;
-    r = next;
-    if (last) break;
+    if (!br.advance(r, upper ? r + step : r - step)) break;
   }
   return r;
 }
@@ -258,7 +230,7 @@ __global__ __launch_bounds__(kThreads) void quantile_kernel(const int64_t* __res
   double target;
   if (is_log) {
     target = v;
-    if (v > kLogHalf && v <= 0.0) target = log(-expm1(v)), up = !up;
+    if (v > num::kLogHalf && v <= 0.0) target = log(-expm1(v)), up = !up;
   } else {
     target = log(v);
     if (v > 0.5 && v <= 1.0) target = log(1.0 - v), up = !up;
@@ -333,14 +305,14 @@ __global__ __launch_bounds__(kThreads) void steps_kernel(const T* __restrict__ e
   double sw = 0.0, cw = 0.0, sx = 0.0, cx = 0.0;
   for (int k = 0; k < K; ++k) {
     const double w = (double)sizes[k];
-    fit::comp_add(sw, cw, w);
-    fit::comp_add(sx, cx, w * (double)row[k * stride_k]);
+    num::comp_add(sw, cw, w);
+    num::comp_add(sx, cx, w * (double)row[k * stride_k]);
   }
   const double n = (double)K, W = sw + cw, xw = (sx + cx) / W;
   double sa = 0.0, ca = 0.0;
   for (int k = 0; k < K; ++k) {
     const double e = (double)sizes[k] * ((double)row[k * stride_k] - xw);
-    fit::comp_add(sa, ca, e * e);
+    num::comp_add(sa, ca, e * e);
   }
   mean[s] = xw;
   se[s] = n / ((n - 1.0) * (W * W)) * (sa + ca);

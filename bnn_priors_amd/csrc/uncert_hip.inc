@@ -2,7 +2,7 @@
 // reference has neither).  Two kernels:
 //
 //   rows_kernel  one pass over acc [E][N][C]: calib::ensemble_kernel's (row, class) layout and its very log-sum-exp and
-//                softmax (calib::lse_add4 / lse_add1 / lse_log_mean / row_softmax), so probs / max_prob / pred / hit are
+//                softmax (num::lse_add4 / lse_add1 / lse_log_mean / row_softmax), so probs / max_prob / pred / hit are
 //                its bits.  Beside the running log-sum-exp a thread keeps sum_e p log p of its class, on the same running
 //                maximum and from the same exponentials (one exp per entry, as in ensemble_kernel); the four samples
 //                of a step are also handed over through LDS so that thread (row, j) finds the first argmax of sample j
@@ -20,14 +20,6 @@ constexpr int kPlane = 258;        // doubles between the four samples' planes o
 
 // x exp(x - m) for the term t = exp(x - m) the log-sum-exp has just formed (0 where x = -inf; a NaN stays a NaN)
 __device__ __forceinline__ double x_times(double x, double t) { return x == -INFINITY ? 0.0 : t * x; }
-
-// s + c += v, c collecting what each addition rounds away (Neumaier): the 128-term sums over the classes stay within an
-// ulp or two of their exact value, in a fixed order
-__device__ __forceinline__ void comp_add(double& s, double& c, double v) {
-  const double t = s + v;
-  c += fabs(s) >= fabs(v) ? (s - t) + v : (v - t) + s;
-  s = t;
-}
 
 __global__ __launch_bounds__(256) void rows_kernel(const double* __restrict__ acc, const int64_t* __restrict__ labels,
                                                    int E, int N, int C, double* __restrict__ probs,
@@ -66,7 +58,7 @@ __global__ __launch_bounds__(256) void rows_kernel(const double* __restrict__ ac
       }
       if (live) {
         double f, tm[4];
-        calib::lse_add4(m, s, x[0], x[1], x[2], x[3], f, tm);
+        num::lse_add4(m, s, x[0], x[1], x[2], x[3], f, tm);
         g = g * f;
         g = (((g + x_times(x[0], tm[0])) + x_times(x[1], tm[1])) + x_times(x[2], tm[2])) + x_times(x[3], tm[3]);
       }
@@ -78,7 +70,7 @@ __global__ __launch_bounds__(256) void rows_kernel(const double* __restrict__ ac
         if (live) {
           double f, tm;
           v = a[(size_t)(e + j) * plane];
-          calib::lse_add1(m, s, v, f, tm);
+          num::lse_add1(m, s, v, f, tm);
           g = g * f + x_times(v, tm);
         }
         xb[j * kPlane + t] = v;
@@ -99,23 +91,23 @@ __global__ __launch_bounds__(256) void rows_kernel(const double* __restrict__ ac
     }
   }
   if (live) {
-    row[t] = calib::lse_log_mean(m, s, E);
+    row[t] = num::lse_log_mean(m, s, E);
     hsum[t] = m == -INFINITY ? g : exp(m) * g;    // sum_e p log p of this class (g = 0 where every sample has p = 0)
   }
   __syncthreads();
   const int64_t n = n0 + t;
   if (t < rows && n < N) {
     double* l = row + t * C;
-    calib::row_softmax(l, C, probs + n * C);
-    calib::row_max(l, C, n, labels, conf, pred, hit);
+    num::row_softmax(l, C, probs + n * C);
+    num::row_max(l, C, n, labels, conf, pred, hit);
     const double top = conf[n];
     const int arg = (int)pred[n];
     double second = C == 1 ? 0.0 : -INFINITY, ent = 0.0, ent_c = 0.0, exp_ent = 0.0, exp_c = 0.0;
     for (int k = 0; k < C; ++k) {
       const double p = l[k];
       if (k != arg && p > second) second = p;     // the largest of the others: duplicates of the maximum count
-      comp_add(ent, ent_c, p == 0.0 ? 0.0 : p * log(p));
-      comp_add(exp_ent, exp_c, hsum[t * C + k]);
+      num::comp_add(ent, ent_c, p == 0.0 ? 0.0 : p * log(p));
+      num::comp_add(exp_ent, exp_c, hsum[t * C + k]);
     }
     ent = -(ent + ent_c);
     exp_ent = -(exp_ent + exp_c) / (double)E;
@@ -142,24 +134,6 @@ __global__ __launch_bounds__(256) void rows_kernel(const double* __restrict__ ac
 
 constexpr int kRiskThreads = 1024;
 constexpr int kNone = 0x7fffffff;
-
-struct Add { __device__ double operator()(double a, double b) const { return a + b; } };
-struct Min { __device__ int operator()(int a, int b) const { return min(a, b); } };
-struct Max { __device__ int operator()(int a, int b) const { return max(a, b); } };
-
-// Hillis-Steele scan over one value per thread, in place: inclusive from the front, or (kBack) from the back
-template <typename T, typename Op, bool kBack>
-__device__ __forceinline__ void scan(T* buf, Op op) {
-  const int t = threadIdx.x;
-  for (int off = 1; off < kRiskThreads; off <<= 1) {
-    const int o = kBack ? t + off : t - off;
-    const bool has = o >= 0 && o < kRiskThreads;
-    const T v = has ? buf[o] : buf[t];
-    __syncthreads();
-    if (has) buf[t] = kBack ? op(buf[t], v) : op(v, buf[t]);
-    __syncthreads();
-  }
-}
 
 // scores [n] (higher = more confident), losses [n], perm = sgmcmc_stable_order of scores.  Rank i = 0 .. n-1 counts from
 // the most confident row down: row perm[n - 1 - i].  risk [n] and out[3] = {aurc, mean loss, has_nan} as the header
@@ -193,7 +167,7 @@ __global__ __launch_bounds__(kRiskThreads) void risk_kernel(const double* __rest
   const double top = scores[min(max(perm[n - 1], 0), n - 1)];     // NaN sorts last in the ascending order
   bad |= top != top;
   if (__syncthreads_or(bad)) {
-    const double q = __longlong_as_double(0x7ff8000000000000ll);
+    const double q = num::qnan();
     for (int i = k0; i < k1; ++i) risk[i] = q;
     if (t == 0) { out[0] = q; out[1] = q; out[2] = 1.0; }
     return;
@@ -204,9 +178,9 @@ __global__ __launch_bounds__(kRiskThreads) void risk_kernel(const double* __rest
   before_first[t] = bf;
   before_last[t] = bl;
   __syncthreads();
-  scan<int, Min, true>(first_s, Min());           // the first group start in chunks >= t
-  scan<int, Max, false>(last_s, Max());           // the last group start in chunks <= t
-  scan<double, Add, false>(incl, Add());          // the losses of chunks <= t
+  num::block_scan<int, num::Min, true, kRiskThreads>(first_s, num::Min());       // the first group start in chunks >= t
+  num::block_scan<int, num::Max, false, kRiskThreads>(last_s, num::Max());       // the last group start in chunks <= t
+  num::block_scan<double, num::Add, false, kRiskThreads>(incl, num::Add());      // the losses of chunks <= t
   auto excl = [&](int chunk) { return chunk ? incl[chunk - 1] : 0.0; };
   const double total = incl[kRiskThreads - 1];    // P(n)
   const int nxt = t + 1 < kRiskThreads ? first_s[t + 1] : kNone;

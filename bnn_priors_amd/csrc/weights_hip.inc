@@ -308,16 +308,15 @@ __global__ __launch_bounds__(64) void boot_row_kernel(const double* __restrict__
   for (int k = 0; k < K; ++k) wr[k] = exp(__dsub_rn(zr[k], mx)) / den;
 }
 
-// out [2][K]: mean_b w, then sqrt(var_b z) with ddof 1 in two passes; sums over b as psis::block_sum takes them
-__global__ __launch_bounds__(psis::kTot) void boot_total_kernel(const double* __restrict__ z,
-                                                                const double* __restrict__ w, int64_t B, int K,
-                                                                double* __restrict__ out) {
-  __shared__ double sh[psis::kTot];
+// out [2][K]: mean_b w, then sqrt(var_b z) with ddof 1 in two passes; sums over b as num::block_sum takes them
+__global__ __launch_bounds__(kT) void boot_total_kernel(const double* __restrict__ z, const double* __restrict__ w,
+                                                        int64_t B, int K, double* __restrict__ out) {
+  __shared__ double sh[kT];
   const double dB = (double)B;
   for (int k = 0; k < K; ++k) {
-    const double mw = psis::block_sum(B, sh, [&](int64_t b) { return w[b * K + k]; }) / dB;
-    const double mz = psis::block_sum(B, sh, [&](int64_t b) { return z[b * K + k]; }) / dB;
-    const double ssq = psis::block_sum(B, sh, [&](int64_t b) {
+    const double mw = num::block_sum<kT>(B, sh, [&](int64_t b) { return w[b * K + k]; }) / dB;
+    const double mz = num::block_sum<kT>(B, sh, [&](int64_t b) { return z[b * K + k]; }) / dB;
+    const double ssq = num::block_sum<kT>(B, sh, [&](int64_t b) {
       const double d = __dsub_rn(z[b * K + k], mz);
       return __dmul_rn(d, d);
     });
@@ -442,7 +441,7 @@ extern "C" int sgmcmc_bb_pseudo_bma(const double* P, int64_t model_stride, int m
     SGMCMC_LAUNCH(weights::boot_row_kernel, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, s, (const double*)part,
                   slices, K, N, b0, count, z, w);
   }
-  SGMCMC_LAUNCH(weights::boot_total_kernel, dim3(1), dim3(psis::kTot), 0, s, (const double*)z, (const double*)w, B, K,
+  SGMCMC_LAUNCH(weights::boot_total_kernel, dim3(1), dim3(weights::kT), 0, s, (const double*)z, (const double*)w, B, K,
                 out);
   return (int)hipGetLastError();
 }
