@@ -24,7 +24,7 @@ INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 SOURCES = [os.path.join(_HERE, "csrc", "sgmcmc_hip.hip")]
 SOURCE = SOURCES[0]
 
-ABI_VERSION = 25
+ABI_VERSION = 26
 CHUNK = 4096
 CHUNK_SMALL = 1024
 NSUMS = 6
@@ -193,6 +193,8 @@ RAOB_MAX_F, RAOB_TILE_ROWS, RAOB_MAX_BLOCKS, RAOB_SCALARS = 64, 64, 256, 16
 TEMPER_SCAN, TEMPER_MAX_LEVELS, TEMPER_UNIFORM_A, TEMPER_UNIFORM_U = 256, 16, 100.0, 0.3
 CORR_TILE, CORR_CHUNK, CORR_MAX_V, CORR_MAX_SPLITS, CORR_TARGET_BLOCKS, CORR_MEAN_BLOCKS = 64, 32, 1024, 64, 1024, 512
 CORR_MAX_BATCH, CORR_STATS = 65535, 5
+STEIN_TILE, STEIN_CHUNK, STEIN_MAX_S, STEIN_MAX_SPLITS, STEIN_TARGET_BLOCKS = 64, 32, 1024, 64, 1024
+STEIN_MAX_BATCH, STEIN_STATS, STEIN_MAX_PICKS = 65535, 3, 1 << 20
 
 
 def raob_state_doubles(F):
@@ -456,6 +458,16 @@ EXPORTS = {
     "sgmcmc_corr_finish": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
                                           ctypes.c_int] + [ctypes.c_void_p] * 5),
     "sgmcmc_corr_offdiag": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 3),
+    "sgmcmc_stein_splits": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_int64]),
+    "sgmcmc_stein_gram": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
+                                         ctypes.c_int64, ctypes.c_int64, ctypes.c_int] + [ctypes.c_void_p] * 3),
+    "sgmcmc_stein_reduce": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
+                            + [ctypes.c_void_p] * 3),
+    "sgmcmc_stein_finish": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_void_p,
+                                           ctypes.c_double] + [ctypes.c_void_p] * 4),
+    "sgmcmc_stein_forms": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
+                           + [ctypes.c_void_p] * 4),
+    "sgmcmc_stein_thin": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 3),
     "sgmcmc_gof_workspace_doubles": (ctypes.c_int64, [ctypes.c_int64]),
     "sgmcmc_gof_cdf": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(GofRecord),
                                       ctypes.c_void_p, ctypes.c_void_p]),

@@ -1744,6 +1744,9 @@ int sgmcmc_debug_normals(float* out, int64_t start, int64_t n, uint64_t seed, ui
 // ... and the correlation between the rows, columns or channels of such a stack: means, the centred Gram matrix on the
 // fp64 matrix pipe, cov / corr and the off-diagonal statistics (fp64)
 #include "corr_hip.inc"
+// ... and whether the draws target the right distribution: the kernel Stein discrepancy from the Gram matrix of samples
+// and scores on the fp64 matrix pipe, its quadratic forms for a wild bootstrap, and Stein thinning (fp64)
+#include "stein_hip.inc"
 // ... and how well the fitted families describe them: distribution functions in log space, KS / CvM / AD, Q-Q (fp64)
 #include "gof_hip.inc"
 // ... and whether a chain samples at its temperature: chi-square tails at any size, intervals, coverage, EWMA (fp64)

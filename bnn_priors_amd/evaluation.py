@@ -25,7 +25,7 @@ from . import _capture
 
 __all__ = ("evaluate_model", "evaluate_ood", "predictive_tables", "logit_tables", "ensemble_across_chains",
            "ensemble_metrics", "gather_samples", "evaluate_loo", "evaluate_marglik", "evaluate_uncertainty",
-           "regression_tables", "evaluate_regression")
+           "regression_tables", "evaluate_regression", "evaluate_stein")
 
 
 def _labels_of(dataloader):
@@ -377,6 +377,29 @@ def evaluate_loo(model, dataloader_train, samples, chains=None):
     res, wres = model_comparison.loo_waic(lps, r_eff)
     return {"elpd_loo": res.elpd_loo, "elpd_loo_se": res.se, "p_loo": res.p_loo, "elpd_waic": wres.elpd_waic,
             "p_waic": wres.p_waic, "pareto_k_max": res.k_max, "pareto_k_bad": float(res.n_bad)}
+
+
+def evaluate_stein(model, samples, x_train, y_train, temperature=1., thin_to=None, **kw):
+    """Do the stored samples target the (tempered) posterior?  (stein.py: the kernel Stein discrepancy with the inverse
+    multiquadric kernel and Stein thinning, on the device, fp64.)  ``stein.scores`` differentiates the model's potential
+    on (x_train, y_train) at every sample (``x_train = y_train = None`` for a ``PriorOnlyModel``), ``stein.kernel_matrix``
+    -- which takes ``**kw``: c, beta, workspace_bytes -- forms the Stein matrix of the model's parameters, moved to the
+    current device.  Plain floats ``ksd``, ``v_stat``, ``u_stat``; ``dimension`` and ``nonfinite`` (ints); with
+    ``thin_to = m`` also ``kept`` (the list of the m sample indices Stein thinning keeps, in the order picked) and
+    ``ksd_thinned`` (the KSD of those m).  The statistic loses power as the dimension grows: compare runs of the same
+    model with it.  The reference has no such function."""
+    from . import stein
+    score = stein.scores(model, samples, x_train, y_train, temperature=temperature)
+    x = {k: samples[k][:len(g)].to(device="cuda", dtype=g.dtype) for k, g in score.items()}
+    k = stein.kernel_matrix(x, {name: g.to("cuda") for name, g in score.items()}, **kw)
+    res = stein.ksd(k)
+    out = {"ksd": res.ksd.item(), "v_stat": res.v_stat.item(), "u_stat": res.u_stat.item(), "dimension": k.d,
+           "nonfinite": int(k.nonfinite)}
+    if thin_to is not None:
+        t = stein.thin(k, thin_to)
+        out["kept"] = t.indices.tolist()
+        out["ksd_thinned"] = t.ksd_path[-1].item()
+    return out
 
 
 @torch.no_grad()

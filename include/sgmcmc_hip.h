@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGMCMC_ABI_VERSION 25
+#define SGMCMC_ABI_VERSION 26
 #define SGMCMC_CHUNK 4096 /* default elements per arena chunk = 256 threads x 4 items x 4 elements */
 #define SGMCMC_CHUNK_SMALL 1024 /* small models: one item per thread, 4x more workgroups */
 #define SGMCMC_NSUMS 6
@@ -1667,6 +1667,72 @@ int sgmcmc_corr_finish(const double* slabs, int splits, int R, int V, int64_t n,
                        double* cov, double* corr, uint8_t* zero_variance, void* stream);
 /* stats [R][SGMCMC_CORR_STATS], counts [R][3] of the R matrices corr [R][V][V]. */
 int sgmcmc_corr_offdiag(const double* corr, int R, int V, double* stats, int64_t* counts, void* stream);
+
+/* ---- Kernel Stein discrepancy and Stein thinning (fp64, deterministic) ------------------------------------------------------
+ * Do the draws target the right distribution?  The kernel Stein discrepancy with the inverse multiquadric kernel (Gorham &
+ * Mackey 2017) needs the draws and the gradient of the log target at each draw only.  This is the definition, restated in
+ * tests/stein_reference.py.
+ * Inputs: the samples X [S][D] and the scores G [S][D], g_i = grad log p(x_i), both fp32 or both fp64, unit column stride
+ * and any row stride (x_stride, score_stride, in elements).  Parameters c^2 > 0 and -1 < beta < 0; d is the total dimension
+ * (D, or the sum over the tensors of a dict whose Gram matrices were added).
+ * Anchor: x~_i = x_i - x_0, subtracted in fp64 by the loader (exact for fp32 input): everything below depends on X through
+ * differences only, so a common offset of the samples costs no digits.
+ * Gram pass, on the fp64 matrix pipe: the symmetric Gram matrix gram [2S][2S] of the 2S rows [X~; G], i.e.
+ *     A = X~ X~^T = gram[i][j],   B = X~ G^T, B_ij = x~_i . g_j = gram[i][S + j],   C = G G^T = gram[S + i][S + j].
+ * Stein matrix, entry (i, j) evaluated with i <= j and mirrored (K and r2 are symmetric bit for bit):
+ *     r2_ij = max(0, (A_ii + A_jj) - 2 A_ij)                        (exactly 0 on the diagonal)
+ *     t_ij  = ((B_ii - B_ij) - B_ji) + B_jj                         = (g_i - g_j) . (x_i - x_j)
+ *     u = c^2 + r2_ij;   p0 = u^beta (1 / sqrt(u) for beta = -1/2, else pow);   p1 = p0 / u;   p2 = p1 / u
+ *     K_ij  = (p0 C_ij - 2 beta p1 (t_ij + d)) - 4 beta (beta - 1) p2 r2_ij
+ * K is positive semi-definite up to rounding.  A NaN or Inf anywhere in X or G is counted in nonfinite[0] and makes K, r2
+ * and every statistic NaN.
+ * Statistics of K [S][S] and a batch of weight vectors W [R][S] (W = NULL: R = 1 vector of ones, by the same arithmetic, so
+ * that W = 1 gives v_stat bit for bit):
+ *     rowsum_ri = sum_j W_rj K_ij;   row_mean = rowsum / S;   Q_r = sum_i W_ri rowsum_ri / S^2   (v_stat for W = 1)
+ *     stats [R][SGMCMC_STEIN_STATS] = {Q_r, (sum_i W_ri rowsum_ri - sum_i W_ri^2 K_ii) / (S (S - 1)), Q_r < 0 ? 0 : sqrt(Q_r)}
+ *     = {v_stat, u_stat, ksd} for W = 1.
+ * Thinning (Riabiz et al. 2022): pi_1 = argmin_j K_jj / 2, pi_m = argmin_j [K_jj / 2 + sum_{a < m} K(pi_a, j)]; picks may
+ * repeat, ties go to the smaller index, a NaN objective never wins;  total_m = total_{m-1} + (2 sum_{a < m} K(pi_a, pi_m) +
+ * K(pi_m, pi_m)),  path_m = sqrt(total_m) / m.
+ * Summation order, a function of (S, D) and of the workspace alone (whatever the row strides): coordinates are cut into
+ * chunks of SGMCMC_STEIN_CHUNK; gram is cut into SGMCMC_STEIN_TILE^2 blocks of which the upper triangle is formed; workgroup
+ * `split` of sgmcmc_stein_splits() takes chunks split, split + splits, ... and accumulates them on the fp64 matrix pipe
+ * (v_mfma_f64_16x16x4_f64: four coordinates per instruction, chunk after chunk in one accumulator); sgmcmc_stein_reduce adds
+ * the splits from 0 in ascending order and mirrors the triangle.  splits = min(chunks, SGMCMC_STEIN_MAX_SPLITS,
+ * SGMCMC_STEIN_TARGET_BLOCKS / block pairs, workspace_bytes / (8 (2S)^2)).  Row sums: lane l of a wave adds j = l, l + 64,
+ * ... ascending, then the fixed tree (l += l + 32, ..., l + 1); forms: thread t adds i = t, t + 256, ... ascending, then the
+ * fixed tree (t += t + 128, ..., t + 1); neither depends on R, so a batch gives the bits of R single calls.  The thinning
+ * walk is one workgroup with the running sums in LDS and exactly m trips of a fixed-tree arg-min over (value, index).
+ * No floating-point atomics, no waiting between workgroups; two calls give the same bits.  The caller provides every buffer
+ * (slabs: splits (2S)^2 doubles; counts: splits ceil(2S / TILE) int64; rowsum: R S doubles); nothing is allocated, nothing
+ * synchronises.  Limits: 2 <= S <= SGMCMC_STEIN_MAX_S, 1 <= D < 2^31, strides >= 0, 1 <= splits <= min(chunks,
+ * SGMCMC_STEIN_MAX_SPLITS), 1 <= R <= SGMCMC_STEIN_MAX_BATCH, 1 <= m <= SGMCMC_STEIN_MAX_PICKS, d >= 1; anything else or a
+ * missing pointer returns hipErrorInvalidValue and launches nothing. */
+#define SGMCMC_STEIN_TILE 64
+#define SGMCMC_STEIN_CHUNK 32
+#define SGMCMC_STEIN_MAX_S 1024
+#define SGMCMC_STEIN_MAX_SPLITS 64
+#define SGMCMC_STEIN_TARGET_BLOCKS 1024
+#define SGMCMC_STEIN_MAX_BATCH 65535
+#define SGMCMC_STEIN_STATS 3
+#define SGMCMC_STEIN_MAX_PICKS 1048576
+
+/* Workgroups per block pair of the Gram pass (0: workspace_bytes holds no (2S)^2 doubles; -1: a refused shape). */
+int sgmcmc_stein_splits(int S, int64_t D, int64_t workspace_bytes);
+/* slabs [splits][2S][2S], of which the blocks of the upper triangle are written; counts [splits][ceil(2S / TILE)]. */
+int sgmcmc_stein_gram(const void* x, const void* score, int dtype, int S, int64_t D, int64_t x_stride, int64_t score_stride,
+                      int splits, double* slabs, int64_t* counts, void* stream);
+/* gram [2S][2S] (every entry), nonfinite [1]. */
+int sgmcmc_stein_reduce(const double* slabs, const int64_t* counts, int splits, int S, double* gram, int64_t* nonfinite,
+                        void* stream);
+/* K [S][S] and r2 [S][S] (either may be NULL) of a gram matrix, or of a sum of them; c2_device (may be NULL) overrides c2. */
+int sgmcmc_stein_finish(const double* gram, int S, double d, double c2, const double* c2_device, double beta,
+                        const int64_t* nonfinite, double* K, double* r2, void* stream);
+/* rowsum [R][S], row_mean [R][S] (may be NULL), stats [R][SGMCMC_STEIN_STATS]; W [R][S] or NULL (then R = 1).  Two launches. */
+int sgmcmc_stein_forms(const double* K, int S, const double* W, int R, double* rowsum, double* row_mean, double* stats,
+                       void* stream);
+/* indices [m], path [m]. */
+int sgmcmc_stein_thin(const double* K, int S, int m, int64_t* indices, double* path, void* stream);
 
 /* Test hook: out[i] = spec normal (fp32) of noise index start+i. */
 int sgmcmc_debug_normals(float* out, int64_t start, int64_t n, uint64_t seed, uint32_t stream,
