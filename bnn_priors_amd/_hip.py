@@ -24,7 +24,7 @@ INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 SOURCES = [os.path.join(_HERE, "csrc", "sgmcmc_hip.hip")]
 SOURCE = SOURCES[0]
 
-ABI_VERSION = 26
+ABI_VERSION = 27
 CHUNK = 4096
 CHUNK_SMALL = 1024
 NSUMS = 6
@@ -195,6 +195,9 @@ CORR_TILE, CORR_CHUNK, CORR_MAX_V, CORR_MAX_SPLITS, CORR_TARGET_BLOCKS, CORR_MEA
 CORR_MAX_BATCH, CORR_STATS = 65535, 5
 STEIN_TILE, STEIN_CHUNK, STEIN_MAX_S, STEIN_MAX_SPLITS, STEIN_TARGET_BLOCKS = 64, 32, 1024, 64, 1024
 STEIN_MAX_BATCH, STEIN_STATS, STEIN_MAX_PICKS = 65535, 3, 1 << 20
+# include/sgmcmc_hip.h, "Lanczos" (SGMCMC_LANCZOS_*, SGMCMC_TRIDIAG_MAX_SWEEPS)
+LANCZOS_CHUNK, LANCZOS_ROWS, LANCZOS_MAX_M, LANCZOS_MAX_SPLITS, LANCZOS_MAX_BATCH = 256, 16, 512, 512, 65535
+LANCZOS_WIDTH, LANCZOS_STATE, TRIDIAG_MAX_SWEEPS = 514, 8, 60
 
 
 def raob_state_doubles(F):
@@ -468,6 +471,21 @@ EXPORTS = {
     "sgmcmc_stein_forms": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
                            + [ctypes.c_void_p] * 4),
     "sgmcmc_stein_thin": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 3),
+    "sgmcmc_lanczos_splits": (ctypes.c_int, [ctypes.c_int64, ctypes.c_int64]),
+    "sgmcmc_lanczos_workspace_bytes": (ctypes.c_int64, [ctypes.c_int64, ctypes.c_int64]),
+    "sgmcmc_lanczos_dots": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
+                                           ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    "sgmcmc_lanczos_reduce": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_double]
+                              + [ctypes.c_void_p] * 5),
+    "sgmcmc_lanczos_update": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
+                                             ctypes.c_int, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 4),
+    "sgmcmc_tridiag_eig": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int64]
+                           + [ctypes.c_void_p] * 6),
+    "sgmcmc_lanczos_ritz": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                           ctypes.c_void_p]),
+    "sgmcmc_effdim": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
+                      + [ctypes.c_void_p] * 4),
     "sgmcmc_gof_workspace_doubles": (ctypes.c_int64, [ctypes.c_int64]),
     "sgmcmc_gof_cdf": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.POINTER(GofRecord),
                                       ctypes.c_void_p, ctypes.c_void_p]),

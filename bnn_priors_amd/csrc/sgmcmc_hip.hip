@@ -1747,6 +1747,9 @@ int sgmcmc_debug_normals(float* out, int64_t start, int64_t n, uint64_t seed, ui
 // ... and whether the draws target the right distribution: the kernel Stein discrepancy from the Gram matrix of samples
 // and scores on the fp64 matrix pipe, its quadratic forms for a wild bootstrap, and Stein thinning (fp64)
 #include "stein_hip.inc"
+// ... and how many directions the data determine: Lanczos with full reorthogonalisation, the tridiagonal QL eigensolver,
+// Ritz vectors on the fp64 matrix pipe and the effective dimensionality (fp64)
+#include "lanczos_hip.inc"
 // ... and how well the fitted families describe them: distribution functions in log space, KS / CvM / AD, Q-Q (fp64)
 #include "gof_hip.inc"
 // ... and whether a chain samples at its temperature: chi-square tails at any size, intervals, coverage, EWMA (fp64)

@@ -25,7 +25,7 @@ from . import _capture
 
 __all__ = ("evaluate_model", "evaluate_ood", "predictive_tables", "logit_tables", "ensemble_across_chains",
            "ensemble_metrics", "gather_samples", "evaluate_loo", "evaluate_marglik", "evaluate_uncertainty",
-           "regression_tables", "evaluate_regression", "evaluate_stein")
+           "regression_tables", "evaluate_regression", "evaluate_stein", "evaluate_eff_dim")
 
 
 def _labels_of(dataloader):
@@ -400,6 +400,71 @@ def evaluate_stein(model, samples, x_train, y_train, temperature=1., thin_to=Non
         out["kept"] = t.indices.tolist()
         out["ksd_thinned"] = t.ksd_path[-1].item()
     return out
+
+
+def evaluate_eff_dim(model, dataloader_train, samples, n_eigs=20, n_steps=None, alpha=1.0, what="likelihood", **kw):
+    """How many directions of weight space do the data determine at each stored sample?  (eff_dim.py: Lanczos with full
+    reorthogonalisation, the tridiagonal eigensolver and N_eff = sum lambda / (lambda + alpha) on the device, fp64.)  For
+    every sample: load it, run ``n_steps`` Lanczos steps (default 2 ``n_eigs``, at most D and ``eff_dim.MAX_M``; ``n_eigs =
+    -1``: all D, for D <= MAX_M) on ``eff_dim.model_hvp(model, x, y, what)`` over the loader's rows, batch by batch, and keep
+    the tridiagonal; then ONE batched launch solves all of them.  ``**kw`` goes to the Lanczos loop (seed,
+    workspace_bytes, breakdown_rtol).  Plain floats and lists: ``eff_dim`` (per alpha: the mean over the samples),
+    ``eff_dim_per_sample`` [S][A], ``eigenvalues`` [S][n_eigs] (the largest Ritz values, ascending), ``max_residual`` (the
+    largest Ritz residual estimate among them); ints ``negative`` (Ritz values <= 0 among them), ``restarts``,
+    ``dimension``.  N_eff from the largest Ritz values only is a LOWER bound of the Hessian's (every eigenvalue left out
+    would add a positive term), and the values are only as accurate as the Hessian-vector product: fp32 for an fp32 model.
+    The model's state and mode are left as found.  The reference has no such function."""
+    from . import eff_dim
+    xs, ys = zip(*((b[0], b[1]) for b in dataloader_train))
+    batch = len(xs[0])
+    params = [p for _, p in model.named_parameters()]
+    dev = params[0].device
+    x, y = torch.cat(xs).to(dev), torch.cat(ys).to(dev)
+    D = sum(p.numel() for p in params)
+    if n_eigs == -1:
+        if D > eff_dim.MAX_M:
+            raise ValueError(f"n_eigs = -1 needs D <= {eff_dim.MAX_M}; D = {D}")
+        k = steps = D
+    else:
+        k = eff_dim._check_int(n_eigs, "n_eigs", 1, min(D, eff_dim.MAX_M))
+        steps = min(2 * k if n_steps is None else eff_dim._check_int(n_steps, "n_steps", k), D, eff_dim.MAX_M)
+    if not isinstance(samples, dict) or not samples:
+        raise ValueError("samples must be a non-empty dict of [S, *shape] stacks")
+    S = _n_samples(samples)
+    state = model.state_dict()
+    kept = {n: v.detach().clone() for n, v in state.items() if n in samples}
+    hvp = eff_dim.model_hvp(model, x, y, what, batch_size=batch)
+    if dev.type != "cuda":
+        raise ValueError("the model must be on the device (there is no CPU path)")
+    if set(kw) - {"seed", "workspace_bytes", "breakdown_rtol"}:
+        raise TypeError(f"unexpected arguments {sorted(set(kw) - {'seed', 'workspace_bytes', 'breakdown_rtol'})}")
+    seed = kw.get("seed", 0)
+    workspace_bytes, rtol = kw.get("workspace_bytes", eff_dim.WORKSPACE_BYTES), kw.get("breakdown_rtol")
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(seed)
+    v0 = torch.randn(D, generator=gen, device=dev, dtype=torch.float64)      # the same start vector for every sample
+    alphas, betas, restarts = [], [], 0
+    try:
+        for s in range(S):
+            model.load_state_dict({n: v[s] for n, v in samples.items()}, strict=False)
+            step, m, r, bad = eff_dim._iterate(hvp, steps, v0, seed, workspace_bytes, rtol)
+            if bad:
+                raise ValueError(f"sample {s}: the Hessian-vector product has {bad} non-finite elements")
+            alphas.append(step.alpha[:m].clone())
+            betas.append(step.beta[:m].clone())
+            restarts += r
+    finally:
+        model.load_state_dict(kept, strict=False)
+    a, b = torch.stack(alphas), torch.stack(betas)
+    theta, Y, _, failed = eff_dim.tridiag_eig(a, b)
+    if int(failed.sum()):
+        raise RuntimeError("sgmcmc_tridiag_eig: an eigenvalue was not deflated after 60 sweeps")
+    m = a.shape[1]
+    top = theta[:, m - k:]
+    n_eff, nonpos, _ = eff_dim.effective_dimensionality(top, alpha)
+    resid = (b[:, m - 1, None] * Y[:, m - 1, m - k:]).abs()
+    return {"eff_dim": n_eff.mean(dim=0).tolist(), "eff_dim_per_sample": n_eff.tolist(), "eigenvalues": top.tolist(),
+            "max_residual": resid.max().item(), "negative": int(nonpos.sum()), "restarts": restarts, "dimension": D}
 
 
 @torch.no_grad()

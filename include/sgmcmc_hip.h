@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGMCMC_ABI_VERSION 26
+#define SGMCMC_ABI_VERSION 27
 #define SGMCMC_CHUNK 4096 /* default elements per arena chunk = 256 threads x 4 items x 4 elements */
 #define SGMCMC_CHUNK_SMALL 1024 /* small models: one item per thread, 4x more workgroups */
 #define SGMCMC_NSUMS 6
@@ -1733,6 +1733,70 @@ int sgmcmc_stein_forms(const double* K, int S, const double* W, int R, double* r
                        void* stream);
 /* indices [m], path [m]. */
 int sgmcmc_stein_thin(const double* K, int S, int m, int64_t* indices, double* path, void* stream);
+
+/* ---- Lanczos, tridiagonal eigenvalues and the effective dimensionality (fp64, deterministic) --------------------------------
+ * How many directions of weight space do the data determine?  N_eff(alpha) = sum_i lambda_i / (lambda_i + alpha) over the
+ * positive eigenvalues of a Hessian (MacKay 1992; Maddox et al. 2020), from the Ritz values of m Lanczos steps with full
+ * reorthogonalisation.  The matrix-vector product is the caller's.  This is the definition, restated in
+ * tests/eff_dim_reference.py.
+ * One step, given the orthonormal rows V_0 .. V_j of V (fp64, unit column stride, any row stride v_stride in elements) and
+ * w = A V_j (fp64, contiguous, updated in place):
+ *     pass p = 1, 2:   c_k = V_k . w  for k = 0 .. j  (sgmcmc_lanczos_dots, sgmcmc_lanczos_reduce with pass = p - 1), then
+ *                      w <- w - sum_k c_k V_k, k ascending, one fma per term       (sgmcmc_lanczos_update, mode 0)
+ *     alpha_j = c_j(1) + c_j(2);   beta_j = sqrt(w . w) after the second pass;   scale = max(scale, |alpha_j|, beta_j)
+ *     no breakdown:  beta_j > rtol scale.  Then V_j+1 = w (1 / beta_j) (sgmcmc_lanczos_update, mode 1), else beta_j is
+ *     written as exactly 0 and state[3] = 1: the host puts a fresh vector into w and runs the same calls with restart = 1
+ *     (no alpha, beta, scale; no breakdown: the norm after > rtol times the norm before the two passes).
+ * state [SGMCMC_LANCZOS_STATE] doubles: {scale, 1 / beta, beta, breakdown (0 / 1), non-finite elements of w seen so far, the
+ * norm of w before the first pass}; the caller zeroes it once.  coef [2][SGMCMC_LANCZOS_MAX_M]: the c of the two passes.
+ * Summation order, a function of (D, workspace_bytes) alone: coordinates are cut into chunks of SGMCMC_LANCZOS_CHUNK, one
+ * coordinate per thread; workgroup `split` of sgmcmc_lanczos_splits() = min(chunks, SGMCMC_LANCZOS_MAX_SPLITS,
+ * workspace_bytes / (8 SGMCMC_LANCZOS_WIDTH)) takes chunks split, split + splits, ..., a thread adds its coordinate of them in
+ * that order (fma), lane l of a wave adds lane l + 32, ..., l + 1, the four waves are added from 0, and the reduce launch
+ * adds the workgroups from 0.  Neither the row stride nor j enters; no floating-point atomics; two calls give the same bits.
+ * ws: splits rows of SGMCMC_LANCZOS_WIDTH doubles {c_0 .. c_MAX_M-1, w . w, non-finite}: sgmcmc_lanczos_workspace_bytes().
+ * sgmcmc_tridiag_eig: `batch` symmetric tridiagonal matrices (diagonal alpha[b ld + i], off-diagonal beta[b ld + i], i < m - 1)
+ * by implicit QL with Wilkinson shifts, one workgroup each, d, e and a sweep's rotations in LDS; work [batch][m][m] holds the
+ * eigenvector matrix transposed while it is rotated.  theta[b ld + p] ascending (ties by original index), Y [batch][m][m]
+ * with column p the eigenvector of theta_p, sweeps[b], failed[b] = 1 (and NaN outputs) if an eigenvalue is not deflated after
+ * SGMCMC_TRIDIAG_MAX_SWEEPS sweeps or is NaN.  e_i is negligible when |e_i| <= eps (|d_i| + |d_i+1|).
+ * sgmcmc_lanczos_ritz: U [D][k] = V^T Y[:, col0 .. col0 + k) on the fp64 matrix pipe (v_mfma_f64_16x16x4_f64), the sum over
+ * the m rows in ascending groups of four; column j is multiplied by -1 where Y[0][col0 + j] < 0 and, with positive != 0, set
+ * to exact zeros where theta[col0 + j] <= m eps max(|theta_0|, |theta_m-1|).
+ * sgmcmc_effdim: out[b][a] = sum over eigs[b][i] > 0 of eigs / (eigs + alphas[a]) by compensated sums (thread t of 256 adds
+ * i = t, t + 256, ..., thread 0 adds the threads from 0); nonpos[b], nonfinite[b] count the finite entries <= 0 and the NaN /
+ * Inf entries, which are left out.
+ * Limits: 1 <= D < 2^31, 1 <= rows, m <= SGMCMC_LANCZOS_MAX_M, 1 <= splits <= min(chunks, SGMCMC_LANCZOS_MAX_SPLITS), batch,
+ * A <= SGMCMC_LANCZOS_MAX_BATCH; anything else or a missing pointer returns hipErrorInvalidValue and launches nothing.  The
+ * caller provides every buffer; nothing is allocated and nothing synchronises. */
+#define SGMCMC_LANCZOS_CHUNK 256
+#define SGMCMC_LANCZOS_ROWS 16
+#define SGMCMC_LANCZOS_MAX_M 512
+#define SGMCMC_LANCZOS_MAX_SPLITS 512
+#define SGMCMC_LANCZOS_MAX_BATCH 65535
+#define SGMCMC_LANCZOS_WIDTH 514
+#define SGMCMC_LANCZOS_STATE 8
+#define SGMCMC_TRIDIAG_MAX_SWEEPS 60
+
+/* Workgroups along D of the step kernels (0: workspace_bytes holds no row of partials; -1: a refused shape). */
+int sgmcmc_lanczos_splits(int64_t D, int64_t workspace_bytes);
+/* Bytes of ws for that many workgroups (-1: a refused shape). */
+int64_t sgmcmc_lanczos_workspace_bytes(int64_t D, int64_t workspace_bytes);
+/* ws[split][k] = partial V_k . w, k < rows; ws[split][MAX_M] = partial w . w; ws[split][MAX_M + 1] = non-finite elements. */
+int sgmcmc_lanczos_dots(const double* V, int64_t v_stride, int rows, const double* w, int64_t D, int splits, double* ws,
+                        void* stream);
+/* pass 0 / 1: coef[pass][k], k < rows; pass 2: alpha[j], beta[j] (unless restart) and state. */
+int sgmcmc_lanczos_reduce(const double* ws, int splits, int rows, int pass, int j, int restart, double rtol, double* coef,
+                          double* alpha, double* beta, double* state, void* stream);
+/* mode 0: w -= sum_k coef[k] V_k and ws[split][MAX_M] = partial w . w afterwards; mode 1: v_next [D] = w * state[1]. */
+int sgmcmc_lanczos_update(const double* V, int64_t v_stride, int rows, double* w, int64_t D, int splits, const double* coef,
+                          int mode, const double* state, double* v_next, double* ws, void* stream);
+int sgmcmc_tridiag_eig(const double* alpha, const double* beta, int batch, int m, int64_t ld, double* theta, double* Y,
+                       double* work, int* sweeps, int* failed, void* stream);
+int sgmcmc_lanczos_ritz(const double* V, int64_t v_stride, int m, int64_t D, const double* Y, const double* theta, int col0,
+                        int k, int positive, double* U, void* stream);
+int sgmcmc_effdim(const double* eigs, int64_t B, int k, const double* alphas, int A, double* out, int64_t* nonpos,
+                  int64_t* nonfinite, void* stream);
 
 /* Test hook: out[i] = spec normal (fp32) of noise index start+i. */
 int sgmcmc_debug_normals(float* out, int64_t start, int64_t n, uint64_t seed, uint32_t stream,
