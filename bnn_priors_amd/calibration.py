@@ -128,6 +128,10 @@ def calibration_metrics(labels, probs, metrics=("ece", "ace", "rmsce"), num_bins
     [N, C] against ``labels`` [N], as a dict of floats, with one host synchronisation at the end.  ``ece`` and
     ``rmsce`` share one ordering of the max-probs.
 
+    ``probs`` of shape [N, 1] is the binary problem: the column p becomes ``[[1 - p, p]]`` in fp64 before anything else,
+    as the reference's ``update_state`` does, and ``labels`` are 0 / 1.  (``ensemble_probs`` keeps C = 1 as it is: the
+    softmax of one class is 1.)
+
     A NaN anywhere in the probabilities gives NaN for every metric.  (The reference's numpy code would drop such rows
     through its ``> 0`` filter and report a number over the rest; a NaN ensemble is reported as such here.)"""
     metrics = tuple(metrics)
@@ -136,6 +140,8 @@ def calibration_metrics(labels, probs, metrics=("ece", "ace", "rmsce"), num_bins
     num_bins = _check_bins(num_bins)
     probs = _probs(probs)
     labels = _labels(labels, probs)
+    if probs.shape[1] == 1:                         # calibration_error.py:204-210: one column p is [[1 - p, p]]
+        probs = torch.cat([1.0 - probs, probs], 1)
     N, C = probs.shape
     dev = probs.device
     rms_bins = num_bins if datapoints_per_bin is None else _check_bins(int(N / datapoints_per_bin))
