@@ -24,7 +24,7 @@ INCLUDE_DIR = os.path.join(os.path.dirname(_HERE), "include")
 SOURCES = [os.path.join(_HERE, "csrc", "sgmcmc_hip.hip")]
 SOURCE = SOURCES[0]
 
-ABI_VERSION = 27
+ABI_VERSION = 28
 CHUNK = 4096
 CHUNK_SMALL = 1024
 NSUMS = 6
@@ -183,6 +183,7 @@ DIAG_MAX_SEQ, DIAG_MAX_CHAINS, DIAG_LAG_BLOCK, DIAG_TILE = 512, 64, 32, 32
 RANK_OWN, RANK_MAX_PROBS = 16, 3
 SUMMARY_MAX_DRAWS, SUMMARY_MAX_TILE = 16384, 64
 PSIS_MIN_DRAWS, PSIS_MAX_DRAWS, PSIS_MAX_TAIL, PSIS_OWN, PSIS_POINTWISE, PSIS_TOTALS = 5, 32768, 544, 16, 6, 9
+POWERSCALE_MAX_DRAWS, POWERSCALE_TILE_CELLS = 8192, 8192
 WEIGHTS_SLICE, WEIGHTS_MAX_MODELS, WEIGHTS_STATE, WEIGHTS_NOISE_PURPOSE = 1024, 32, 72, 4
 GMIX_TILE, GMIX_MAX_SAMPLES, GMIX_MAX_QUANTILES, PIT_MAX_LEVELS = 128, 32768, 64, 1024
 FIT_TILE_DOUBLES, FIT_TILE_ROWS, FIT_MAX_BLOCKS, FIT_PART, FIT_STATE = 5120, 512, 1024, 408, 1288
@@ -430,6 +431,12 @@ EXPORTS = {
                         + [ctypes.c_void_p] * 5),
     "sgmcmc_psis_totals": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p,
                                           ctypes.c_void_p]),
+    "sgmcmc_powerscale_tile_quantities": (ctypes.c_int, [ctypes.c_int]),
+    "sgmcmc_powerscale_sort": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int,
+                                              ctypes.c_int, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p]),
+    "sgmcmc_powerscale_distance": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64,
+                                                  ctypes.c_void_p, ctypes.c_int, ctypes.c_int64] + [ctypes.c_void_p] * 4),
     "sgmcmc_weights_workspace_bytes": (ctypes.c_int64, [ctypes.c_int, ctypes.c_int64, ctypes.c_int64, ctypes.c_int]),
     "sgmcmc_stacking_init": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64,
                                             ctypes.c_double, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p,

@@ -435,4 +435,45 @@ __device__ double block_sum(int64_t N, double* sh, F f) {
   return sh[0];
 }
 
+// The compare-exchange walk of the column sorts (summary::sort_kernel, powerscale::sort_kernel): a bitonic network along
+// the rows of an LDS tile [n_pad][1 << log_tq] (n_pad a power of two), every column ascending.  q is the fastest index of
+// the tile AND of the thread numbering: a step with distance j pairs row i (bit j clear) with row i + j, thread p takes
+// column p % TQ of pair p / TQ, so no lane group strides along the rows (summary_hip.inc has the bank argument).
+// kKeyed: key [n_pad][TQ] travels with its value and breaks ties, the smaller key first -- with distinct keys a total
+// order, so the result does not depend on the network.  Without keys equal values are interchangeable.  Called by the
+// whole workgroup after the tile is written (the walk begins with a barrier); the caller synchronises before reading.
+template <bool kKeyed, int kThreads>
+__device__ __forceinline__ void bitonic_walk(double* __restrict__ tile, uint16_t* __restrict__ key, int n_pad,
+                                             int log_tq) {
+  const int t = threadIdx.x, tq = 1 << log_tq;
+  const int pairs = (n_pad << log_tq) >> 1;
+  for (int k = 2; k <= n_pad; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      __syncthreads();
+      for (int p = t; p < pairs; p += kThreads) {
+        const int c = p & (tq - 1), pr = p >> log_tq;
+        const int i = ((pr & ~(j - 1)) << 1) | (pr & (j - 1));        // bit j clear; the partner is i + j
+        const int lo = (i << log_tq) | c, hi = ((i | j) << log_tq) | c;
+        const double a = tile[lo], b = tile[hi];
+        const bool ascending = (i & k) == 0;                           // always in the last merge, k = n_pad
+        if constexpr (kKeyed) {
+          const uint16_t ka = key[lo], kb = key[hi];
+          const bool above = a > b || (a == b && ka > kb), below = a < b || (a == b && ka < kb);
+          if (ascending ? above : below) {
+            tile[lo] = b;
+            tile[hi] = a;
+            key[lo] = kb;
+            key[hi] = ka;
+          }
+        } else {
+          if (ascending ? a > b : a < b) {
+            tile[lo] = b;
+            tile[hi] = a;
+          }
+        }
+      }
+    }
+  }
+}
+
 }  // namespace num

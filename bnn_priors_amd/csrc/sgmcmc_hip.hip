@@ -1737,6 +1737,8 @@ int sgmcmc_debug_normals(float* out, int64_t start, int64_t n, uint64_t seed, ui
 #include "summary_hip.inc"
 // model comparison from the same tables: PSIS-LOO with Pareto-k and WAIC, pointwise and in total (fp64)
 #include "psis_hip.inc"
+// ... and whether the prior matters: power-scaling sensitivity, a keyed column sort and the weighted-ECDF distance (fp64)
+#include "powerscale_hip.inc"
 // model-averaging weights from the pointwise elpd rows: stacking, pseudo-BMA, pseudo-BMA+ and mixture densities (fp64)
 #include "weights_hip.inc"
 // the data-driven priors fitted to stacks of weight samples: moments, multivariate-t EM, element-wise families (fp64)

@@ -91,23 +91,7 @@ __global__ __launch_bounds__(kSortThreads) void sort_kernel(const T* __restrict_
     tile[e] = v;
   }
 
-  const int pairs = cells >> 1;
-  for (int k = 2; k <= n_pad; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      __syncthreads();
-      for (int p = t; p < pairs; p += kSortThreads) {
-        const int c = p & (tq - 1), pr = p >> log_tq;
-        const int i = ((pr & ~(j - 1)) << 1) | (pr & (j - 1));        // bit j clear; the partner is i + j
-        const int lo = (i << log_tq) | c, hi = ((i | j) << log_tq) | c;
-        const double a = tile[lo], b = tile[hi];
-        const bool ascending = (i & k) == 0;                           // always in the last merge, k = n_pad
-        if (ascending ? a > b : a < b) {
-          tile[lo] = b;
-          tile[hi] = a;
-        }
-      }
-    }
-  }
+  num::bitonic_walk<false, kSortThreads>(tile, nullptr, n_pad, log_tq);        // written once, with the keyed sort's
   __syncthreads();
 
   for (int e = t; e < (N << log_tq); e += kSortThreads) {

@@ -25,7 +25,8 @@ from . import _capture
 
 __all__ = ("evaluate_model", "evaluate_ood", "predictive_tables", "logit_tables", "ensemble_across_chains",
            "ensemble_metrics", "gather_samples", "evaluate_loo", "evaluate_marglik", "evaluate_uncertainty",
-           "regression_tables", "evaluate_regression", "evaluate_stein", "evaluate_eff_dim")
+           "regression_tables", "evaluate_regression", "evaluate_stein", "evaluate_eff_dim",
+           "evaluate_prior_sensitivity")
 
 
 def _labels_of(dataloader):
@@ -465,6 +466,72 @@ def evaluate_eff_dim(model, dataloader_train, samples, n_eigs=20, n_steps=None, 
     resid = (b[:, m - 1, None] * Y[:, m - 1, m - k:]).abs()
     return {"eff_dim": n_eff.mean(dim=0).tolist(), "eff_dim_per_sample": n_eff.tolist(), "eigenvalues": top.tolist(),
             "max_residual": resid.max().item(), "negative": int(nonpos.sum()), "restarts": restarts, "dimension": D}
+
+
+def evaluate_prior_sensitivity(model, dataloader_train, dataloader_test, samples, chains=None, per_prior=False,
+                               weights=False, alpha=1.01, threshold=0.05):
+    """Does the prior matter for this posterior, and for which quantities?  (prior_sensitivity.py: power-scaling
+    sensitivity from the stored samples -- a keyed column sort and the weighted-ECDF distance on the device, fp64, the
+    weights by ``model_comparison.psis``.)  Every sample is loaded and ``model.log_prior()`` recorded in fp64: the
+    component ``"prior"``; with ``per_prior=True`` every prior module's ``log_prob()`` is a component of its own,
+    ``"prior:<module name>"`` (selective power-scaling).  The component ``"likelihood"`` is the row sum of
+    ``predictive_tables(model, dataloader_train, samples)``' ``lps``.  The quantities are the test table
+    ``lps [E, N_test]``; with ``weights=True`` also every stacked floating-point tensor of ``samples``.  ``chains=M``:
+    ``samples`` hold M chains of equal length one after the other (``gather_samples``' layout).
+
+    Plain floats and lists: ``components[name]`` = ``sensitive_fraction`` (the share of the quantities with psi >=
+    threshold), ``psi_max``, ``psi_median``, ``pareto_k`` (of the powers 1 / alpha and alpha); ``diagnosis`` = how many
+    quantities read ``none``, ``conflict`` (prior-data conflict) and ``strong_prior`` (strong prior or weak
+    likelihood); ``quantities``; ``pareto_k_bad``: how many of the components' Pareto-k exceed
+    ``model_comparison.k_threshold(E)`` -- there is no moment matching, so for those the chain has to be rerun under the
+    scaled prior.  The model's state and mode are left as found.  The reference has no such function."""
+    from . import model_comparison, prior, prior_sensitivity
+    if not isinstance(samples, dict) or not samples:
+        raise ValueError("samples must be a non-empty dict of [S, *shape] stacks")
+    E = _n_samples(samples)
+    M = 1 if chains is None else int(chains)
+    if M < 1 or E % M:
+        raise ValueError(f"{E} samples do not hold {chains} chains of equal length")
+    dev = next(iter(model.parameters())).device
+    if dev.type != "cuda":
+        raise ValueError("the model must be on the device (there is no CPU path)")
+    state = model.state_dict()
+    kept = {n: v.detach().clone() for n, v in state.items() if n in samples}
+    training = model.training
+    parts = {"prior": torch.empty(E, dtype=torch.float64, device=dev)}
+    if per_prior:
+        parts.update({f"prior:{n}": torch.empty(E, dtype=torch.float64, device=dev) for n, _ in prior.named_priors(model)})
+    try:
+        with torch.no_grad():
+            for s in range(E):
+                model.load_state_dict({n: v[s] for n, v in samples.items()}, strict=False)
+                parts["prior"][s] = model.log_prior().double()
+                if per_prior:
+                    for n, pr in prior.named_priors(model):
+                        parts[f"prior:{n}"][s] = torch.as_tensor(pr.log_prob()).double()
+        parts["likelihood"] = predictive_tables(model, dataloader_train, samples)[0][:E].sum(1)
+        tables = [predictive_tables(model, dataloader_test, samples)[0][:E]]
+    finally:
+        model.load_state_dict(kept, strict=False)
+        model.train(training)
+    if weights:
+        tables += [v[:E].to(dev) for v in samples.values() if v.is_floating_point() and v[0].numel()]
+    results = [prior_sensitivity.power_scale_sensitivity(t.unflatten(0, (M, E // M)), parts, alpha, threshold)
+               for t in tables]
+    out = {"alpha": float(alpha), "threshold": float(threshold), "components": {}}
+    for name in parts:
+        psi = torch.cat([r.components[name].psi.reshape(-1) for r in results])
+        out["components"][name] = {"sensitive_fraction": int((psi >= threshold).sum()) / psi.numel(),
+                                   "psi_max": psi.max().item(), "psi_median": psi.median().item(),
+                                   "pareto_k": results[0].components[name].pareto_k.tolist()}
+    codes = torch.cat([r.diagnosis.reshape(-1) for r in results])
+    out["diagnosis"] = {key: int((codes == code).sum()) for key, code in
+                        (("none", prior_sensitivity.NONE), ("conflict", prior_sensitivity.CONFLICT),
+                         ("strong_prior", prior_sensitivity.STRONG_PRIOR))}
+    out["quantities"] = codes.numel()
+    limit = model_comparison.k_threshold(E)
+    out["pareto_k_bad"] = sum(k > limit for c in out["components"].values() for k in c["pareto_k"])
+    return out
 
 
 @torch.no_grad()

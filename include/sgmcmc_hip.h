@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define SGMCMC_ABI_VERSION 27
+#define SGMCMC_ABI_VERSION 28
 #define SGMCMC_CHUNK 4096 /* default elements per arena chunk = 256 threads x 4 items x 4 elements */
 #define SGMCMC_CHUNK_SMALL 1024 /* small models: one item per thread, 4x more workgroups */
 #define SGMCMC_NSUMS 6
@@ -1289,6 +1289,65 @@ int sgmcmc_psis_loo(const void* table, int is_f64, int is_ratio, int64_t draw_st
 /* The totals of pointwise [SGMCMC_PSIS_POINTWISE][N] as sgmcmc_psis_loo wrote it.  One launch of one workgroup. */
 int sgmcmc_psis_totals(const double* pointwise, int64_t observations, double k_threshold, double* totals,
                        void* stream);
+
+/* ---- Power-scaling sensitivity: does the prior matter? (fp64, deterministic) -------------------------------------------
+ * Kallioinen, Paananen, Buerkner, Vehtari 2023 (the R package priorsense).  The reference has no such function; this is
+ * the definition -- it governs, not the R package -- restated in tests/powerscale_reference.py.  The prior, or the
+ * likelihood, is raised to a power alpha near 1 by importance-reweighting the stored draws (log ratios
+ * (alpha - 1) log p, smoothed by sgmcmc_psis_loo with is_ratio); what this section adds is how far every quantity's
+ * weighted distribution moves.
+ * x[m][s][q]: `chains` (M) x `draws` (S) x `quantities` (Q), fp32 (is_f64 = 0) or fp64, element (m, s, q) at
+ * x[m * chain_stride + s * draw_stride + q], read in place.  Draw t = m S + s, N = M S; there is no splitting.  fp32 is
+ * widened on load, all arithmetic is fp64, every operation is rounded once (nothing is contracted into an fma).
+ * Keyed sort (sgmcmc_powerscale_sort): every column is sorted ascending by value, ties by ascending draw index t -- a
+ * total order, so the result is unique.  sorted[i][q] (fp64) is the value and order[i][q] (uint16) the draw index at rank
+ * i.  -0.0 counts as, and is written as, +0.0.  A column with a non-finite draw is NaN throughout `sorted`; its `order`
+ * is unspecified (but below N).
+ * Weighted distance and moments (sgmcmc_powerscale_distance): w[t][a], `vectors` (A) weight vectors, fp64, linear (not
+ * log) and non-negative, element (t, a) at weights[t * A + a].  For vector a and quantity q, v_i = sorted[i][q] and
+ * w_i = w[order[i][q]][a]:
+ *   W        sum_t w[t][a] over ascending t from +0.0, one accumulator (a function of a only)
+ *   C_i      sum_{k <= i} w_k over ascending i from +0.0;  for i = 0 .. N-2:
+ *            Q_i = C_i / W,  P_i = (double)(i + 1) / N,  d_i = v_(i+1) - v_i,  s_i = P_i + Q_i,
+ *            delta_i = (Q_i - P_i) / s_i
+ *   g(delta) (1 - delta) log1p(-delta) + (1 + delta) log1p(delta) with 0 (-inf) = 0, so g(+-1) = 2 ln 2:
+ *            |delta| < 1/4: the series sum_{k=1..16} delta^2k / (k (2k - 1)) by Horner in x = delta delta,
+ *            acc = 0; for k = 16 .. 1: acc = (acc + c_k) x, c_k the double nearest 1 / (k (2k - 1));
+ *            otherwise t1 = (1 - delta) log1p(-delta) (0 for delta >= 1), t2 = (1 + delta) log1p(delta) (0 for
+ *            delta <= -1), g = t1 + t2.  (The plain form P log2(P / M) + Q log2(Q / M) cancels at alpha near 1 and is
+ *            not used.)
+ *   den      sum_i d_i s_i;  num = (sum_i (d_i s_i) g(delta_i)) / SGMCMC_POWERSCALE_TWO_LN2;  dist = sqrt(num / den):
+ *            the normalised cumulative Jensen-Shannon distance between the unweighted and the weighted ECDF, in [0, 1]
+ *   wmean    (sum_i w_i v_i) / W over i = 0 .. N-1;  wsd = sqrt((sum_i w_i ((v_i - wmean) (v_i - wmean))) / W)
+ * Every term is non-negative; every sum runs over ascending i from +0.0 with one accumulator.  dist, wmean and wsd are
+ * [A][Q] fp64, element (a, q) at out[a * out_stride + q].
+ * Rules: a column with a non-finite draw gives NaN in all three.  A weight vector with a non-finite or negative entry, or
+ * whose W is not a positive finite number, gives NaN for all its quantities.  A column whose draws are all equal gives
+ * dist = 0 (den = 0), wmean = that value and wsd = 0.  A zero weight is legal.
+ * log1p is the only operation not fixed to the bit by this text, and it enters only where |delta| >= 1/4.
+ * The caller provides every buffer (sorted and order of a chunk of quantities: 10 bytes per draw and quantity); nothing
+ * is allocated, nothing synchronises, everything runs on the given stream; no atomics; a quantity's result depends on
+ * its own column and its weight vector only, whatever the grid, the tile or the chunk.  Limits:
+ * SGMCMC_PSIS_MIN_DRAWS <= N <= SGMCMC_POWERSCALE_MAX_DRAWS, 1 <= A <= 65535, out_stride >= Q; anything else or a NULL
+ * pointer returns hipErrorInvalidValue and launches nothing. */
+#define SGMCMC_POWERSCALE_MAX_DRAWS 8192  /* N: one column of the sort's LDS tile; the weight vector is 64 KiB of LDS */
+#define SGMCMC_POWERSCALE_TILE_CELLS 8192 /* cells of the sort's tile, an fp64 value and a uint16 index each: 80 KiB */
+#define SGMCMC_POWERSCALE_TWO_LN2 1.3862943611198906 /* the double nearest 2 ln 2 */
+
+/* TQ, the quantities per workgroup of sgmcmc_powerscale_sort at N = total_draws:
+ * min(64, SGMCMC_POWERSCALE_TILE_CELLS / N_pad), N_pad the next power of two (at least 8); 0 for an N that is refused.
+ * Host arithmetic only. */
+int sgmcmc_powerscale_tile_quantities(int total_draws);
+/* sorted [N][quantities] (fp64) and order [N][quantities] (uint16), both contiguous.  One launch: a workgroup stages an
+ * [N_pad][TQ] tile of values and draw indices in LDS, pads it with (+inf, own row) after deciding the non-finite rule, and
+ * sorts its columns with the bitonic network of sgmcmc_summary_sort, the indices travelling with their values. */
+int sgmcmc_powerscale_sort(const void* x, int is_f64, int64_t chain_stride, int64_t draw_stride, int chains, int draws,
+                           int64_t quantities, double* sorted, uint16_t* order, void* stream);
+/* dist, wmean, wsd from `sorted` and `order` as sgmcmc_powerscale_sort wrote them for N = total_draws.  One launch, lane
+ * = quantity, one grid row per weight vector, the vector staged in LDS. */
+int sgmcmc_powerscale_distance(const double* sorted, const uint16_t* order, int total_draws, int64_t quantities,
+                               const double* weights, int vectors, int64_t out_stride, double* dist, double* wmean,
+                               double* wsd, void* stream);
 
 /* ---- Model averaging: stacking, pseudo-BMA and pseudo-BMA+ weights (fp64, deterministic) ------------------------------
  * Yao, Vehtari, Simpson, Gelman 2018.  The reference has no such function; this is the definition, restated in
