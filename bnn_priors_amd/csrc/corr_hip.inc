@@ -1,50 +1,26 @@
 // Weight-correlation analysis (include/sgmcmc_hip.h, "Correlation between the variables of a stack"): per-variable means,
 // the centred Gram matrix G = d d^T on the fp64 matrix pipe, cov / corr and the off-diagonal statistics of a correlation
-// matrix.  Included from sgmcmc_hip.hip after numerics_hip.inc (it uses num::comp_add and num::qnan).
+// matrix.  Included from sgmcmc_hip.hip after numerics_hip.inc (it uses num::comp_add and num::qnan) and gram_hip.inc,
+// which has the pieces the Gram pass shares with stein_hip.inc, its LDS layout and the MFMA lane map.
 //
 // One loader serves the mean and the Gram pass: a tile of kTile variables x kChunk observations is read through the
 // strided geometry with consecutive lanes on consecutive addresses -- along the variables when the variable stride is the
 // smaller one (v_major), else along the observations -- and staged in LDS as tile[variable][observation] in fp64.  All
 // arithmetic then reads the LDS tile, so the summation order is a function of (V, n) alone, whatever the strides are.
-// Row stride kChunk + 2 doubles: the 32 lanes of one ds_read_b64 group hold 16 variables x 2 observations, at double
-// offsets 34 v + k = 2 v + k (mod 32), which are 32 different bank pairs.
-//
-// v_mfma_f64_16x16x4_f64: lane l gives A[i = l & 15][k = l >> 4] and B[k = l >> 4][j = l & 15] and receives
-// D[i = (l >> 4) + 4 reg][j = l & 15], reg = 0 .. 3 (NOT the fp32 map; tests/test_weight_correlation.py's V = 17 and
-// V = 65 cases would put 3 of 4 results in the wrong row otherwise).  A workgroup of 4 waves forms one 64 x 64 block,
-// wave w the 32 x 32 quadrant (w >> 1, w & 1) as 2 x 2 MFMA tiles: 16 accumulated doubles per lane.
 
 namespace corr {
 
-constexpr int kThreads = 256;
-constexpr int kTile = SGMCMC_CORR_TILE;
-constexpr int kChunk = SGMCMC_CORR_CHUNK;
-constexpr int kRow = kChunk + 2;                        // LDS row stride in doubles (see above)
+using gram::kThreads, gram::kTile, gram::kChunk, gram::kRow, gram::kPerThread, gram::tiles_of, gram::chunks_of;
 constexpr int kMaxV = SGMCMC_CORR_MAX_V;
 constexpr int kMaxSplits = SGMCMC_CORR_MAX_SPLITS;
 constexpr int kTargetBlocks = SGMCMC_CORR_TARGET_BLOCKS;
 constexpr int kMeanBlocks = SGMCMC_CORR_MEAN_BLOCKS;
 constexpr int kMaxBatch = SGMCMC_CORR_MAX_BATCH;
 constexpr int kStats = SGMCMC_CORR_STATS;
-constexpr int kPerThread = kTile * kChunk / kThreads;   // elements of a tile a thread loads
 constexpr int64_t kMaxN = ((int64_t)1 << 31) - 1;
-static_assert(kTile == 64 && kChunk % 4 == 0 && kPerThread * kThreads == kTile * kChunk, "tile geometry");
-static_assert(kThreads % kTile == 0 && kThreads % kChunk == 0 && kChunk <= 64, "loader geometry");
 typedef sgmcmc_corr_geometry Geom;
-typedef double f64x4 __attribute__((ext_vector_type(4)));
 
-inline int tiles_of(int V) { return (V + kTile - 1) / kTile; }
-inline int64_t chunks_of(int64_t n) { return (n + kChunk - 1) / kChunk; }
-inline int splits(int V, int64_t n, int64_t workspace_bytes) {
-  const int nb = tiles_of(V), pairs = nb * (nb + 1) / 2;
-  int64_t s = chunks_of(n);
-  if (s > kMaxSplits) s = kMaxSplits;
-  const int fill = kTargetBlocks / pairs;               // (>= 7: pairs <= 136)
-  if (s > fill) s = fill;
-  const int64_t fit = workspace_bytes / ((int64_t)sizeof(double) * V * V);
-  if (s > fit) s = fit;
-  return (int)(s < 0 ? 0 : s);
-}
+inline int splits(int V, int64_t n, int64_t ws) { return gram::splits(V, n, ws, kMaxSplits, kTargetBlocks); }
 inline int mean_blocks(int V, int64_t n) {
   const int64_t chunks = chunks_of(n), cap = kMeanBlocks / tiles_of(V);
   return (int)(chunks < cap ? chunks : cap);
@@ -185,7 +161,7 @@ __global__ __launch_bounds__(kThreads) void gram_kernel(const T* __restrict__ x,
   __shared__ double sB[kTile * kRow];
   __shared__ double sMean[2 * kTile];
   __shared__ int64_t sOff[2][kChunk];
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int t = threadIdx.x;
   const int nb = (g.V + kTile - 1) / kTile;
   int p = blockIdx.x, bi = 0;
   while (p >= nb - bi) {                                // block pair p of the upper triangle, row-major
@@ -206,9 +182,10 @@ __global__ __launch_bounds__(kThreads) void gram_kernel(const T* __restrict__ x,
   T ra[kPerThread], rb[kPerThread];
   load_tile(x, g, va, sOff[0], valid_of(g, c), ra);
   if (!diag) load_tile(x, g, vb, sOff[0], valid_of(g, c), rb);
-  f64x4 acc[4];
+  gram::f64x4 acc[4];
 #pragma unroll
-  for (int q = 0; q < 4; ++q) acc[q] = f64x4{0.0, 0.0, 0.0, 0.0};
+  for (int q = 0; q < 4; ++q) acc[q] = gram::f64x4{0.0, 0.0, 0.0, 0.0};
+  const int lane = t & 63, wave = t >> 6;
   const double* tb = diag ? sA : sB;
   const double* pa = sA + ((wave >> 1) * 32 + (lane & 15)) * kRow + (lane >> 4);
   const double* pb = tb + ((wave & 1) * 32 + (lane & 15)) * kRow + (lane >> 4);
@@ -254,13 +231,10 @@ __global__ __launch_bounds__(kThreads) void finish_kernel(const double* __restri
   const int idx = blockIdx.x * kThreads + threadIdx.x, rep = blockIdx.y, R = gridDim.y;
   if (idx >= V * V) return;
   const int i = idx / V, j = idx - i * V, a = i < j ? i : j, b = i < j ? j : i;
-  double gab = 0.0, gaa = 0.0, gbb = 0.0;
-  for (int s = 0; s < splits; ++s) {
-    const double* slab = slabs + ((size_t)s * R + rep) * V * V;
-    gab += slab[(size_t)a * V + b];
-    gaa += slab[(size_t)a * V + a];
-    gbb += slab[(size_t)b * V + b];
-  }
+  const size_t at[3] = {(size_t)a * V + b, (size_t)a * V + a, (size_t)b * V + b};
+  double gs[3];
+  gram::slab_sums(slabs + (size_t)rep * V * V, splits, (size_t)R * V * V, at, gs);
+  const double gab = gs[0], gaa = gs[1], gbb = gs[2];
   const bool bad = nonfinite && nonfinite[0] != 0, flat = gaa == 0.0 || gbb == 0.0;
   const size_t o = (size_t)rep * V * V + idx;
   if (cov) cov[o] = bad ? num::qnan() : flat ? 0.0 : gab / denom;
@@ -371,8 +345,7 @@ extern "C" int sgmcmc_corr_gram(const void* x, int dtype, const sgmcmc_corr_geom
       (dtype != SGMCMC_F32 && dtype != SGMCMC_F64))
     return (int)hipErrorInvalidValue;
   const corr::Geom g = *geometry;
-  const int nb = corr::tiles_of(g.V);
-  const dim3 grid(nb * (nb + 1) / 2, splits, R), block(corr::kThreads);
+  const dim3 grid = gram::pair_grid(g.V, splits, R), block(corr::kThreads);
   if (dtype == SGMCMC_F32)
     SGMCMC_LAUNCH(corr::gram_kernel<float>, grid, block, 0, (hipStream_t)stream, (const float*)x, g, batch_stride, mean,
                   corr::chunks_of(g.n), slabs);

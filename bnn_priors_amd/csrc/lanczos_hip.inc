@@ -8,8 +8,7 @@
 // splits, ... and every thread accumulates its coordinate of them in that order; a workgroup's threads are then added by the
 // fixed tree of wave_sum / block_sum below and sgmcmc_lanczos_reduce adds the workgroups' partials from 0 upwards.  Nothing
 // depends on the row stride or on how many rows there are, and there are no floating-point atomics.
-// The Ritz GEMM follows stein_hip.inc's conventions for v_mfma_f64_16x16x4_f64: A[i = l & 15][k = l >> 4],
-// B[k = l >> 4][j = l & 15], D[i = (l >> 4) + 4 reg][j = l & 15].
+// The Ritz GEMM uses the lane map of v_mfma_f64_16x16x4_f64 that gram_hip.inc's header sets out.
 
 namespace lanczos {
 
@@ -27,7 +26,7 @@ constexpr int kAhead = 8;                               // rows of the eigenvect
 constexpr int64_t kMaxD = ((int64_t)1 << 31) - 1;
 constexpr int kRitzCoords = 64, kRitzCols = 16, kRitzK = 32, kRitzStride = kRitzCoords + 16;
 static_assert(kChunk == kThreads && kWidth >= kMaxM + 2 && kState >= 6 && kMaxM % kThreads == 0, "step geometry");
-typedef double f64x4 __attribute__((ext_vector_type(4)));
+using gram::f64x4;
 
 inline int64_t chunks_of(int64_t D) { return (D + kChunk - 1) / kChunk; }
 inline bool shape_ok(int64_t D) { return D >= 1 && D <= kMaxD; }

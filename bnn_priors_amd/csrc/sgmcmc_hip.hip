@@ -1743,6 +1743,9 @@ int sgmcmc_debug_normals(float* out, int64_t start, int64_t n, uint64_t seed, ui
 #include "weights_hip.inc"
 // the data-driven priors fitted to stacks of weight samples: moments, multivariate-t EM, element-wise families (fp64)
 #include "fit_hip.inc"
+// what the Gram passes of the next two share on the fp64 matrix pipe: geometry, splits rule, block-pair decode, the
+// chunk multiply, the slab store and the slab sum (each keeps its own chunk loop)
+#include "gram_hip.inc"
 // ... and the correlation between the rows, columns or channels of such a stack: means, the centred Gram matrix on the
 // fp64 matrix pipe, cov / corr and the off-diagonal statistics (fp64)
 #include "corr_hip.inc"

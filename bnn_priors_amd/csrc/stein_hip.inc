@@ -1,48 +1,28 @@
 // Kernel Stein discrepancy and Stein thinning (include/sgmcmc_hip.h, "Kernel Stein discrepancy"): the Gram matrix of the
 // 2S rows [X - x_0; G] on the fp64 matrix pipe, the Stein matrix K of the inverse multiquadric kernel, its row sums and
-// quadratic forms, and the greedy thinning walk.  Included from sgmcmc_hip.hip after numerics_hip.inc (it uses num::qnan).
+// quadratic forms, and the greedy thinning walk.  Included from sgmcmc_hip.hip after numerics_hip.inc (it uses num::qnan)
+// and gram_hip.inc, which has the pieces the Gram pass shares with corr_hip.inc, its LDS layout and the MFMA lane map.
 //
-// The Gram pass follows corr_hip.inc: a tile of kTile rows x kChunk coordinates is staged in LDS as tile[row][coordinate]
-// in fp64 with row stride kChunk + 2 doubles (the 32 lanes of one ds_read_b64 group hold 16 rows x 2 coordinates at double
-// offsets 34 r + k = 2 r + k (mod 32): 32 different bank pairs), and v_mfma_f64_16x16x4_f64 takes A[i = l & 15][k = l >> 4]
-// and B[k = l >> 4][j = l & 15] and returns D[i = (l >> 4) + 4 reg][j = l & 15].  What differs: the rows are samples and
-// the contraction runs over the coordinates, which have unit stride, so consecutive lanes always walk coordinates; row r of
-// the 2S is sample r of X less the anchor x_0 (r < S) or score r - S (r >= S), decided row by row, since the X / G boundary
-// falls inside a tile whenever S is no multiple of kTile; and nothing is centred per row.
+// What this Gram pass brings to the walk: the rows are samples and the contraction runs over the coordinates (unit stride:
+// consecutive lanes always walk coordinates); row r of the 2S is sample r of X less the anchor x_0 (r < S) or score r - S
+// (r >= S), decided row by row, since the X / G boundary falls inside a tile whenever S is no multiple of kTile.
 
 namespace stein {
 
-constexpr int kThreads = 256;
-constexpr int kTile = SGMCMC_STEIN_TILE;
-constexpr int kChunk = SGMCMC_STEIN_CHUNK;
-constexpr int kRow = kChunk + 2;                        // LDS row stride in doubles (see above)
+using gram::kThreads, gram::kTile, gram::kChunk, gram::kRow, gram::kPerThread, gram::tiles_of, gram::chunks_of;
 constexpr int kMaxS = SGMCMC_STEIN_MAX_S;
 constexpr int kMaxSplits = SGMCMC_STEIN_MAX_SPLITS;
 constexpr int kTargetBlocks = SGMCMC_STEIN_TARGET_BLOCKS;
 constexpr int kMaxBatch = SGMCMC_STEIN_MAX_BATCH;
 constexpr int kStats = SGMCMC_STEIN_STATS;
 constexpr int kMaxPicks = SGMCMC_STEIN_MAX_PICKS;
-constexpr int kPerThread = kTile * kChunk / kThreads;   // elements of a tile a thread loads: rows t / kChunk + 8 i
-constexpr int kRowStep = kThreads / kChunk;
+constexpr int kRowStep = kThreads / kChunk;            // a thread's elements of a tile: rows t / kChunk + kRowStep i
 constexpr int kOwn = kMaxS / kThreads;                  // candidates a thread of the thinning walk owns
 constexpr int64_t kMaxD = ((int64_t)1 << 31) - 1;
-static_assert(kTile == 64 && kChunk % 4 == 0 && kPerThread * kThreads == kTile * kChunk, "tile geometry");
-static_assert(kThreads % kChunk == 0 && kChunk <= 64 && kOwn * kThreads == kMaxS, "loader geometry");
-typedef double f64x4 __attribute__((ext_vector_type(4)));
+static_assert(kOwn * kThreads == kMaxS, "thinning geometry");
 
-inline int tiles_of(int V) { return (V + kTile - 1) / kTile; }
-inline int64_t chunks_of(int64_t D) { return (D + kChunk - 1) / kChunk; }
 inline bool shape_ok(int S, int64_t D) { return S >= 2 && S <= kMaxS && D >= 1 && D <= kMaxD; }
-inline int splits(int S, int64_t D, int64_t workspace_bytes) {
-  const int V = 2 * S, nb = tiles_of(V), pairs = nb * (nb + 1) / 2;
-  int64_t s = chunks_of(D);
-  if (s > kMaxSplits) s = kMaxSplits;
-  const int fill = kTargetBlocks / pairs;               // (>= 1: pairs <= 528)
-  if (s > fill) s = fill;
-  const int64_t fit = workspace_bytes / ((int64_t)sizeof(double) * V * V);
-  if (s > fit) s = fit;
-  return (int)(s < 0 ? 0 : s);
-}
+inline int splits(int S, int64_t D, int64_t ws) { return gram::splits(2 * S, D, ws, kMaxSplits, kTargetBlocks); }
 
 // row r of the 2S at coordinate col (< D): the element, as stored
 template <typename T>
@@ -90,8 +70,8 @@ __global__ __launch_bounds__(kThreads) void gram_kernel(const T* __restrict__ x,
   __shared__ double sA[kTile * kRow];
   __shared__ double sB[kTile * kRow];
   __shared__ int sBad;
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int V = 2 * S, nb = (V + kTile - 1) / kTile;
+  const int t = threadIdx.x, V = 2 * S;
+  const int nb = (V + kTile - 1) / kTile;
   int p = blockIdx.x, bi = 0;
   while (p >= nb - bi) {                                // block pair p of the upper triangle, row-major
     p -= nb - bi;
@@ -109,9 +89,10 @@ __global__ __launch_bounds__(kThreads) void gram_kernel(const T* __restrict__ x,
   }
   load_tile(x, g, S, D, xs, gs, va, c, ra);
   if (!diag) load_tile(x, g, S, D, xs, gs, vb, c, rb);
-  f64x4 acc[4];
+  gram::f64x4 acc[4];
 #pragma unroll
-  for (int q = 0; q < 4; ++q) acc[q] = f64x4{0.0, 0.0, 0.0, 0.0};
+  for (int q = 0; q < 4; ++q) acc[q] = gram::f64x4{0.0, 0.0, 0.0, 0.0};
+  const int lane = t & 63, wave = t >> 6;
   const double* tb = diag ? sA : sB;
   const double* pa = sA + ((wave >> 1) * 32 + (lane & 15)) * kRow + (lane >> 4);
   const double* pb = tb + ((wave & 1) * 32 + (lane & 15)) * kRow + (lane >> 4);
@@ -167,9 +148,10 @@ __global__ __launch_bounds__(kThreads) void reduce_kernel(const double* __restri
   }
   if (idx >= V * V) return;
   const int i = idx / V, j = idx - i * V, a = i < j ? i : j, b = i < j ? j : i;
-  double s = 0.0;
-  for (int q = 0; q < splits; ++q) s += slabs[(size_t)q * V * V + (size_t)a * V + b];
-  gram[idx] = s;
+  const size_t at[1] = {(size_t)a * V + b};
+  double s[1];
+  gram::slab_sums(slabs, splits, (size_t)V * V, at, s);
+  gram[idx] = s[0];
 }
 
 // ---- 3. finish: r2 and the Stein matrix K of gram = [[A, B], [B^T, C]], entry (i, j) evaluated as (min, max) ---------------
@@ -309,8 +291,7 @@ extern "C" int sgmcmc_stein_gram(const void* x, const void* score, int dtype, in
   if (!x || !score || !slabs || !counts || !stein::shape_ok(S, D) || x_stride < 0 || score_stride < 0 || splits < 1 ||
       splits > stein::kMaxSplits || splits > stein::chunks_of(D) || (dtype != SGMCMC_F32 && dtype != SGMCMC_F64))
     return (int)hipErrorInvalidValue;
-  const int nb = stein::tiles_of(2 * S);
-  const dim3 grid(nb * (nb + 1) / 2, splits), block(stein::kThreads);
+  const dim3 grid = gram::pair_grid(2 * S, splits), block(stein::kThreads);
   if (dtype == SGMCMC_F32)
     SGMCMC_LAUNCH(stein::gram_kernel<float>, grid, block, 0, (hipStream_t)stream, (const float*)x, (const float*)score, S, D,
                   x_stride, score_stride, stein::chunks_of(D), slabs, (long long*)counts);

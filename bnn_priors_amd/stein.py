@@ -24,7 +24,7 @@ import math
 
 import torch
 
-from . import _hip
+from . import _gram_pass, _hip
 from .calibration import _stream
 
 __all__ = ("SteinKernel", "KSD", "SteinTest", "Thinning", "scores", "kernel_matrix", "ksd", "quadratic_forms",
@@ -58,9 +58,7 @@ Thinning.__doc__ = ("indices [m] (int64): the kept samples in the order they wer
 def splits(S, D, workspace_bytes=WORKSPACE_BYTES):
     """Workgroups that share the chunks of one block pair of the Gram pass (``stein::splits``): workgroup b walks chunks
     b, b + splits, ...  A function of (S, D, workspace_bytes) alone; 0 if the workspace holds no 2S x 2S doubles."""
-    nb = -(-2 * S // TILE)
-    return max(0, min(-(-D // CHUNK), MAX_SPLITS, _hip.STEIN_TARGET_BLOCKS // (nb * (nb + 1) // 2),
-                      workspace_bytes // (8 * 4 * S * S)))
+    return _gram_pass.splits(2 * S, D, workspace_bytes, TILE, CHUNK, MAX_SPLITS, _hip.STEIN_TARGET_BLOCKS)
 
 
 # ---------------------------------------------------------------------------------------------------------------- scores
@@ -184,8 +182,7 @@ def _check_c(c):
 
 
 def _check_workspace(workspace_bytes, S):
-    if isinstance(workspace_bytes, bool) or not isinstance(workspace_bytes, int) or workspace_bytes < 0:
-        raise ValueError(f"workspace_bytes = {workspace_bytes!r} must be a non-negative integer")
+    _gram_pass.check_workspace_bytes(workspace_bytes)
     if workspace_bytes < 32 * S * S:
         raise ValueError(f"workspace_bytes = {workspace_bytes} holds no {2 * S} x {2 * S} matrix of doubles "
                          f"({32 * S * S} bytes)")

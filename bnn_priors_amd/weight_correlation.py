@@ -21,7 +21,7 @@ import math
 
 import torch
 
-from . import _hip
+from . import _gram_pass, _hip
 from .calibration import _stream
 from .prior_fit import _collapse
 
@@ -60,9 +60,7 @@ LayerCorrelations.__doc__ = ("layers: {(name, axis): IndependenceTest}; skipped:
 def splits(V, n, workspace_bytes=WORKSPACE_BYTES):
     """Workgroups that share the chunks of one block pair of the Gram pass (``corr::splits``): workgroup b walks chunks
     b, b + splits, ...  A function of (V, n, workspace_bytes) alone; 0 if the workspace holds no V x V doubles."""
-    nb = -(-V // TILE)
-    return max(0, min(-(-n // CHUNK), MAX_SPLITS, _hip.CORR_TARGET_BLOCKS // (nb * (nb + 1) // 2),
-                      workspace_bytes // (8 * V * V)))
+    return _gram_pass.splits(V, n, workspace_bytes, TILE, CHUNK, MAX_SPLITS, _hip.CORR_TARGET_BLOCKS)
 
 
 def mean_blocks(V, n):
@@ -109,8 +107,7 @@ def _contiguous_geometry(V, n):
 def _check_common(g, ddof, workspace_bytes):
     if isinstance(ddof, bool) or not isinstance(ddof, int) or not 0 <= ddof < g.n:
         raise ValueError(f"ddof = {ddof!r}: 0 .. n - 1 = {g.n - 1} is supported")
-    if isinstance(workspace_bytes, bool) or not isinstance(workspace_bytes, int) or workspace_bytes < 0:
-        raise ValueError(f"workspace_bytes = {workspace_bytes!r} must be a non-negative integer")
+    _gram_pass.check_workspace_bytes(workspace_bytes)
     sp = splits(g.V, g.n, workspace_bytes)
     if sp < 1:
         raise ValueError(f"workspace_bytes = {workspace_bytes} holds no {g.V} x {g.V} matrix of doubles "

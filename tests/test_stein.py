@@ -690,3 +690,29 @@ def test_evaluate_stein_equals_the_separate_calls():
         x = {n: v.numpy() for n, v in smp.items()}
         want = ref.ksd_stats(ref.stein_matrix(x, {n: v.numpy() for n, v in stein.scores(model, smp).items()}, wide=True)["K"])
         assert got["ksd"] == pytest.approx(float(want["ksd"]), rel=1e-9)
+
+
+@pytest.mark.gpu
+def test_the_gram_walk_reproduces_the_recorded_bits():
+    """sha256 of K, r2 and nonfinite of ``kernel_matrix`` and of the thinning order of 5 picks, for every case of
+    tests/golden/make_gram_bits.py, against tests/golden/gram_bits.json -- recorded with the library of the commit before
+    the two Gram passes came to share csrc/gram_hip.inc.  The library is built with -ffp-contract=off: the same operations
+    in the same order are the same bits."""
+    import importlib.util
+    import json
+    import os
+    spec = importlib.util.spec_from_file_location(
+        "make_gram_bits", os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "make_gram_bits.py"))
+    bits = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bits)
+    with open(bits.PATH) as fh:
+        recorded = json.load(fh)
+    assert len(recorded["parent_commit"]) == 40 and len(recorded["library_sha"]) == 16
+    want, got = recorded["stein"], bits.stein_digests()
+    assert sorted(got) == sorted(want) == sorted(bits.stein_cases())
+    for name in sorted(got):
+        assert sorted(got[name]) == sorted(want[name]) == ["K", "nonfinite", "r2", "thin"]
+        for array in got[name]:
+            assert got[name][array] == want[name][array], (
+                f"case {name}: {array} differs from the recording (recorded under {recorded['versions']}, running "
+                f"{bits.versions()})")

@@ -198,6 +198,38 @@ def test_module_constants_are_the_ones_the_shapes_are_built_on():
     assert lib.sgmcmc_corr_splits(1025, 10, 1 << 20) == -1 and lib.sgmcmc_corr_splits(4, 1, 1 << 20) == -1
 
 
+def test_gram_splits_are_the_formulas_from_before_the_shared_helper():
+    """``_gram_pass.splits`` and the two public ``splits`` against the formulas that ``weight_correlation.splits`` and
+    ``stein.splits`` spelled out before they shared it, restated literally (TILE 64, CHUNK 32, 64 splits at most, 1,024
+    target blocks), at the edges of every term: V around the tile, lengths around the chunk and at the limit, workspaces
+    around one V x V matrix of doubles."""
+    from bnn_priors_amd import _gram_pass, _hip, stein, weight_correlation as wc
+    assert (wc.TILE, wc.CHUNK, wc.MAX_SPLITS, _hip.CORR_TARGET_BLOCKS) == (64, 32, 64, 1024)
+    assert (stein.TILE, stein.CHUNK, stein.MAX_SPLITS, _hip.STEIN_TARGET_BLOCKS) == (64, 32, 64, 1024)
+
+    def corr_before(V, n, workspace_bytes):
+        nb = -(-V // 64)
+        return max(0, min(-(-n // 32), 64, 1024 // (nb * (nb + 1) // 2), workspace_bytes // (8 * V * V)))
+
+    def stein_before(S, D, workspace_bytes):
+        nb = -(-2 * S // 64)
+        return max(0, min(-(-D // 32), 64, 1024 // (nb * (nb + 1) // 2), workspace_bytes // (8 * 4 * S * S)))
+
+    seen = set()
+    for V in (1, 64, 65, 1024, 2048):
+        for length in (1, 31, 32, 33, 2 ** 20, 2 ** 31 - 1):
+            for ws in (0, 8 * V * V - 1, 8 * V * V, 256 << 20):
+                want = corr_before(V, length, ws)
+                assert _gram_pass.splits(V, length, ws, 64, 32, 64, 1024) == want == wc.splits(V, length, ws), (V, length, ws)
+                assert stein.splits(V, length, ws) == stein_before(V, length, ws), (V, length, ws)
+                if V % 2 == 0:                               # the same matrix as stein's 2S rows
+                    assert stein.splits(V // 2, length, ws) == want, (V, length, ws)
+                seen.add(want)
+    assert {0, 1, 2, 7, 64} <= seen                          # every term of the minimum decides somewhere
+    assert wc.splits(130, 4101) == corr_before(130, 4101, wc.WORKSPACE_BYTES) == 64
+    assert stein.splits(65, 215) == stein_before(65, 215, stein.WORKSPACE_BYTES) == 7
+
+
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_restatement_against_numpy(name):
     x = ref.as_matrix(_stack(name), CASES[name][2])
@@ -556,3 +588,29 @@ def test_layer_correlations_equal_the_per_tensor_calls():
             assert torch.equal(_bits(p), _bits(q))
     chains = [{k: v[i::3] for k, v in samples.items()} for i in range(3)]
     assert sorted(wc.layer_correlations(chains, replicates=3).layers) == sorted(out.layers)
+
+
+@pytest.mark.gpu
+def test_the_gram_walk_reproduces_the_recorded_bits():
+    """sha256 of mean, cov, corr, zero_variance, nonfinite and the off-diagonal statistics of every case of
+    tests/golden/make_gram_bits.py, and of its batched permutation cases, against tests/golden/gram_bits.json -- recorded
+    with the library of the commit before the two Gram passes came to share csrc/gram_hip.inc.  The library is built with
+    -ffp-contract=off: the same operations in the same order are the same bits."""
+    import importlib.util
+    import json
+    import os
+    spec = importlib.util.spec_from_file_location(
+        "make_gram_bits", os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "make_gram_bits.py"))
+    bits = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bits)
+    with open(bits.PATH) as fh:
+        recorded = json.load(fh)
+    assert len(recorded["parent_commit"]) == 40 and len(recorded["library_sha"]) == 16
+    want, got = recorded["corr"], bits.corr_digests()
+    assert sorted(got) == sorted(want) and len(got) == len(bits.corr_cases()) + 3
+    for name in sorted(got):
+        assert sorted(got[name]) == sorted(want[name])
+        for array in got[name]:
+            assert got[name][array] == want[name][array], (
+                f"case {name}: {array} differs from the recording (recorded under {recorded['versions']}, running "
+                f"{bits.versions()})")
